@@ -102,6 +102,9 @@ def parse(argv=None):
                     help='item table sharded by row over the ranks (args.shard_tables; implies --row-sparse): the N4 path')
     ap.add_argument('--row-sparse', action='store_true',
                     help='touched-rows-only zero/clip/Adam/exchange (args.row_sparse_adam); always on for c5')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step gave its caller (loss, updated parameters, '
+                         'gradients) as DIR/<name>.npy, float32, at most 64 MB in all (fixed seeded row samples of large tensors)')
     return ap.parse_args(argv)
 
 
@@ -368,9 +371,53 @@ def cpu_baseline_rtm(wl, n_steps):
 
 
 # ------------------------------------------------------------------------------------------ one workload
-def measure(a, name, rank, world, dev, steps, warmup, reps, extras, cpu_steps, items=0):
+DUMP_BUDGET_BYTES = 64 << 20
+# Not dumped: the attention's key bias.  Softmax is unchanged by a shift common to every key, so its gradient is exactly zero
+# and what a run holds there is rounding noise (fp32 atomics sum in a different order every run) that Adam scales to +-lr per
+# step: neither the gradient nor the parameter is a function of the inputs (the parity tests skip it for the same reason).
+DUMP_NO_SIGNAL = ('linear_keys.bias',)
+
+
+def dump_outputs(out_dir, loss, model, write=True):
+    """What the last timed step handed its caller — the loss, every parameter after the optimizer step and every gradient
+    the backward left (except DUMP_NO_SIGNAL) — as out_dir/<name>.npy in float32.  A tensor larger than its share of the 64 MB budget is stored as
+    a fixed sample of its rows (numpy generator seeded by the tensor's name, rows in ascending order), so that two builds
+    run with the same arguments can be compared file for file.  Every rank calls this (with a sharded item table the state
+    dict is a collective); only the one with write=True writes.  Returns the file names written."""
+    import zlib
+    import numpy as np
+    arrays = [('loss', loss.detach())]
+    with torch.no_grad():
+        for k, v in sorted(model.state_dict().items()):
+            if torch.is_tensor(v) and v.is_floating_point() and not k.endswith(DUMP_NO_SIGNAL):
+                arrays.append(('param.' + k, v))
+        for k, p in sorted(model.named_parameters()):
+            if p.grad is not None and not k.endswith(DUMP_NO_SIGNAL):
+                arrays.append(('grad.' + k, p.grad))
+        if not write:
+            return None
+        cap = max(1024, DUMP_BUDGET_BYTES // 4 // len(arrays))      # elements per array: the total stays within the budget
+        os.makedirs(out_dir, exist_ok=True)
+        names, total = [], 0
+        for k, t in arrays:
+            t = t.detach()
+            if t.numel() > cap:
+                rows = t.reshape(t.shape[0], -1) if t.dim() >= 2 else t.reshape(-1, 1)
+                keep = max(1, cap // rows.shape[1])
+                rng = np.random.default_rng(zlib.crc32(k.encode()))
+                idx = np.sort(rng.choice(rows.shape[0], size=min(keep, rows.shape[0]), replace=False))
+                t = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+            x = t.float().cpu().numpy()
+            total += x.nbytes
+            np.save(os.path.join(out_dir, k + '.npy'), x)
+            names.append(k + '.npy')
+    assert total <= DUMP_BUDGET_BYTES, total
+    return names
+
+
+def measure(a, name, rank, world, dev, steps, warmup, reps, extras, cpu_steps, items=0, dump_dir=None):
     """Build the workload, time EXACTLY `steps` steps (barrier + synchronize on both sides, max over ranks), then the
-    extra legs; returns the contract dict."""
+    extra legs; returns the contract dict.  dump_dir: the last timed step's outputs are written there (dump_outputs)."""
     from prodsearch_amd import _lib, dist as pdist
     wl = (RtmWorkload if name == 'c4' else TemWorkload)(a, name, rank, dev, items)
     model, optim = wl.model, wl.optim
@@ -408,6 +455,7 @@ def measure(a, name, rank, world, dev, steps, warmup, reps, extras, cpu_steps, i
     torch.cuda.synchronize()
     elapsed = pdist.max_over_ranks(time.perf_counter() - t0, dev)
     last_loss = float(loss.detach())
+    dumped = dump_outputs(dump_dir, loss, model, write=rank == 0) if dump_dir else None
 
     desc, extra_cfg = wl.describe()
     Bw, Kw = wl.B, wl.K
@@ -429,6 +477,8 @@ def measure(a, name, rank, world, dev, steps, warmup, reps, extras, cpu_steps, i
         # N > 1, sharded optimizer: the forms of its two collectives it timed on this node and kept (dist.ShardedAdamExchange._tune)
         "exchange_tuning": getattr(exchange, 'tuned', None),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(dump_dir), "files": len(dumped)}
     if world > 1:
         # comm / compute split (every rank runs it; rank 0 keeps the numbers): a HIP event pair around every collective of the
         # step on the stream it is issued from (dist.comm_timing) and around each whole step, over a further `steps` steps
@@ -735,7 +785,8 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device('cuda', local)
     try:
-        out = measure(a, a.workload, rank, world, dev, a.steps, a.warmup, a.reps, not a.no_extras, a.cpu_steps, a.items)
+        out = measure(a, a.workload, rank, world, dev, a.steps, a.warmup, a.reps, not a.no_extras, a.cpu_steps, a.items,
+                      dump_dir=a.dump_outputs)
     except Exception:
         if world > 1 and not (os.environ.get('PS_DP_RS') == 'rccl' and os.environ.get('PS_DP_AG') == 'rccl'):
             # (this process has initialised the GPU: nothing is retried here.  `python bench.py --gpus N` without torchrun does the

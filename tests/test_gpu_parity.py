@@ -330,7 +330,8 @@ def test_graph_replayed_step_is_bitwise_the_eager_step():
     through the staging prologue) must reproduce the eager step exactly: same kernels, same order."""
     import subprocess, sys, os, json
     code = r"""
-import sys, json, torch
+import sys, json, faulthandler, torch
+faulthandler.enable()                      # a crash of the child names the Python line it happened under
 sys.path.insert(0, %r); sys.path.insert(0, %r)
 from golden_util import Golden
 from prodsearch_amd import ItemTransformerRanker, build_optim, _lib
@@ -355,7 +356,7 @@ print(json.dumps({'graphs': int(_lib.load().ps_graph_replay_enabled()), 'losses'
     for flag in ('0', '1'):
         env = dict(os.environ, PS_GRAPHS=flag)
         r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
+        assert r.returncode == 0, 'PS_GRAPHS=%s: exit %d\n%s\nstdout: %s' % (flag, r.returncode, r.stderr[-3000:], r.stdout[-500:])
         out[flag] = json.loads(r.stdout.strip().splitlines()[-1])
     assert out['0']['graphs'] == 0 and out['1']['graphs'] == 1
     # same parameters, same encoder kernels; the loss itself is summed by the fused forward's epilogue in the eager step and by the
