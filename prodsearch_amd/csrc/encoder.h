@@ -52,6 +52,12 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
                         const float* valid, float* ws, const Ws& w, hipStream_t st, ColFoldList* fold = nullptr,
                         const ScoreArgs* score_on_side = nullptr, bool rows_listed = false);
 
+// What enc_layers_forward / enc_layers_backward hand to their caller's next step (thread-local, tem.hip): every entry point
+// clears them on entry and on its error returns.  enc_take_dx_two_partials: the attention backward left d x as two partial
+// rows per position (dx and dxn, AttnArgs::dxp) — read once, cleared by the read.
+void enc_clear_call_flags();
+bool enc_take_dx_two_partials();
+
 GemmProblem gp(const float* A, int lda, int ta, const float* Bm, int ldb, int tb, float* C, int ldc, int M, int N, int K);
 int run1(const GemmProblem& p, hipStream_t st);
 GemmProblem gp_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int n_out, int k_in, int rows);

@@ -1544,7 +1544,8 @@ static int launch_gemm_impl(const GemmGroup& g, hipStream_t stream) {
   {
     static const int flat_all = ps_diag_int("PS_WGRAD_FLAT_ALL", 1);
     const int ks = g.p[0].ksplit;
-    bool plain = flat_all && !listed && !full && g.p[0].ta == 1 && g.p[0].tb == 1 && ks >= 8 && ks % 8 == 0 && x3_on();
+    // (the flat decode holds at most 3 problems: the deferred K / V / Q + f_W group of the item transformer has 4)
+    bool plain = flat_all && !listed && !full && g.n <= 3 && g.p[0].ta == 1 && g.p[0].tb == 1 && ks >= 8 && ks % 8 == 0 && x3_on();
     for (int i = 0; i < g.n && plain; ++i)
       plain = g.p[i].accumulate == 2 || (g.p[i].accumulate == 0 && g.p[i].split_stride > 0);
     if (plain) {

@@ -1969,6 +1969,7 @@ int launch_embed_scatter(const EmbedBwdArgs& a, hipStream_t st) {
   if (!det) a2.det_dm = nullptr;
   a2.sig = nullptr; a2.sigval = 0;
   PS_REQUIRE(!a.dx2 || (!det && (!fsb || a.fsb_dqe == a.dx)), "embed scatter: a second dx partial needs the default path with d query_emb = row 0 of dx");
+  PS_REQUIRE(!a.dx2 || !a.dqmean_d, "embed scatter: d mean (dqmean_d) is built from one dx partial; a second partial (dx2) would be lost");
   if (fsb) {       // d query_emb as two partials (AttnArgs::dxp): always two reads, the second weighted 0 when there is one buffer
     a2.fsb_dqe2 = a.dx2 ? a.dx2 : a.fsb_dqe;
     a2.fsb_k2 = a.dx2 ? 1.f : 0.f;

@@ -2044,11 +2044,12 @@ extern "C" int ps_rtm_backward(const PsRtmDesc* desc, const PsRtmTensors* params
                                const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev,
                                ps_stream_t stream) {
   const int rc = rtm_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream);
-  if (rc != PS_OK) side_abort();          // never leave the side stream waiting behind a failed call (tem.hip)
+  if (rc != PS_OK) { side_abort(); enc_clear_call_flags(); }    // never leave the side stream waiting behind a failed call (tem.hip)
   return rc;
 }
 static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
                              const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev, ps_stream_t stream) {
+  enc_clear_call_flags();
   PS_REQUIRE(desc && params && batch && ws && grads, "rtm backward: null argument");
   const PsRtmDesc& D = *desc;
   RtmWs r; Ws w; PsTemDesc E; RtmK k;
@@ -2117,6 +2118,7 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   const int eb = rtm_slot_blocks(r);
   if (k.pvc || k.det) k.gs = ws + r.enc_base + w.dx;     // (det + pv encoder: the review rows' gradients are parked in place, scattered below)
   TRY(enc_layers_backward(E, T, TG, nullptr, ws + r.valid, ws + r.enc_base, w, st, &fold, nullptr, rtm_rows_listed(r, w)));
+  PS_REQUIRE(!enc_take_dx_two_partials(), "rtm backward: the encoder left d x as two partials, which nothing here adds");
   if (D.review_encoder == PS_RENC_FS) {
     // through the review projection: d pre = dx * tanh', bias gradient, weight gradient, d raw = d pre . f_W
     PS_REQUIRE(G.rev_fs_w && G.rev_fs_b && params->rev_fs_w, "rtm backward: null review-encoder f_W gradient");

@@ -756,8 +756,15 @@ bool enc_rowlist_taken(const PsTemDesc& D, const Ws& w, bool rows_listed) {
   return attn_sq1_fits(probe);
 }
 
-static bool g_dx_two_partials = false;      // set by enc_layers_backward for the embed backward that follows it (single-thread contract)
-static bool g_split_bwd_deferred = false;   // encode_forward -> enc_layers_forward: the fused projection + attention launch re-splits the backward's streams
+// Decisions handed from one call to the next of the same entry point; cleared at every entry point and on its error returns
+static thread_local bool g_dx_two_partials = false;      // set by enc_layers_backward for the embed backward that follows it
+static thread_local bool g_split_bwd_deferred = false;   // encode_forward -> enc_layers_forward: the fused projection + attention launch re-splits the backward's streams
+void enc_clear_call_flags() { g_dx_two_partials = false; g_split_bwd_deferred = false; }
+bool enc_take_dx_two_partials() {
+  const bool two = g_dx_two_partials;
+  g_dx_two_partials = false;
+  return two;
+}
 // the predicate of enc_layers_forward's fused projection + attention launch, from what encode_forward knows before the embed launch
 static bool kvq_fwd_will_fuse(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed) {
   if (D.model != PS_MODEL_TEM || D.n_layers != 1 || !ps_fusion_enabled()) return false;
@@ -836,7 +843,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
     else TRY(attn_sq1_fits(a) ? launch_attn_fwd_sq1(a, st) : launch_attn_fwd(a, st));
     const bool fuse = ps_fusion_enabled() && i == NL - 1 && l.Sq == 1 && mlp_fused_serves(d, D.F) && w.wsplit &&
                       P.final_ln_g && P.final_ln_b;
-    PS_REQUIRE(!fold_sc || fuse, "forward: folded scoring without the fused last layer");
+    PS_REQUIRE(!fold_sc || fuse || i != NL - 1, "forward: folded scoring without the fused last layer");   // (earlier layers: never fused)
     if (fuse) {   // Wo + LN + W1 + GELU + W2 + final LN of the last layer in one kernel (mlp_fused.hip)
       MlpFwdArgs m;
       memset(&m, 0, sizeof(m));
@@ -895,8 +902,17 @@ struct SamplerArgs { const float* prob; const int32_t* alias; int64_t* items; in
 // (B^2 L / 2 index reads in total): fine up to a few thousand sequences, dense products beyond
 static bool rows_list_ok(const PsTemDesc& D) { return D.L <= 64 && (int64_t)D.B * D.B * D.L <= ((int64_t)64 << 20); }
 
+static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
+                               hipStream_t st, const SamplerArgs* samp, const ScoreArgs* fold_sc);
 static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
                           hipStream_t st, const SamplerArgs* samp = nullptr, const ScoreArgs* fold_sc = nullptr) {
+  enc_clear_call_flags();
+  const int rc = encode_forward_impl(D, P, Bt, ws, w, st, samp, fold_sc);
+  if (rc != PS_OK) enc_clear_call_flags();
+  return rc;
+}
+static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
+                               hipStream_t st, const SamplerArgs* samp, const ScoreArgs* fold_sc) {
   const bool tem = D.model == PS_MODEL_TEM;
   const int B = D.B, d = D.d, S = w.S, NL = tem ? D.n_layers : 0;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
@@ -1320,8 +1336,10 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
       static const bool rows_on0 = ps_env_int("PS_NO_ROWLIST", 0) == 0;
       static const bool dx_fused_on = ps_env_int("PS_KVDX_FUSED", 1) != 0;
       const WSplit kvs = (i == 0 && NL == 1) ? make_wsplit(D, P, ws, w) : WSplit{};
+      // (FS query encoder only: its fused backward reads d query_emb as the two partials; the AVG branch copies one row of dx)
       const bool dx_fused = dx_fused_on && wf && q_folded && i == 0 && NL == 1 && d == 128 && kvs.on && kvs.bwd_kv && !ps_deterministic() &&
-                            rows_on0 && rows_listed && !qall && w.qpos == 0 && w.vrows != 0 && l.n_in == B && attn_bwd_wf_two_partials(a);
+                            rows_on0 && rows_listed && !qall && w.qpos == 0 && w.vrows != 0 && l.n_in == B && attn_bwd_wf_two_partials(a) &&
+                            D.query_encoder == PS_QENC_FS;
       if (dx_fused) { a.kvb_stream = kvs.bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; }
       g_dx_two_partials = dx_fused;
       // valid rows only (below): the dK / dV rows of padded positions are then never read, and never written
@@ -1432,12 +1450,13 @@ extern "C" int ps_tem_backward(const PsTemDesc* desc, const PsTemTensors* params
                                float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
                                ps_stream_t stream) {
   const int rc = tem_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream);
-  if (rc != PS_OK) side_abort();          // never leave the side stream waiting behind a failed call
+  if (rc != PS_OK) { side_abort(); enc_clear_call_flags(); }    // never leave the side stream waiting behind a failed call
   return rc;
 }
 static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                              float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
                              ps_stream_t stream) {
+  enc_clear_call_flags();
   PS_REQUIRE(desc && params && batch && ws && grads, "backward: null argument");
   PsTemDesc D = *desc;
   D.C = 0;
@@ -1488,8 +1507,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   memset(&e, 0, sizeof(e));
   e.B = B; e.Q = D.Q; e.L = D.L; e.S = S; e.d = d; e.P = D.product_size; e.V = D.vocab_size; e.tem = tem;
   e.qw = batch->query_word_idxs; e.ui = batch->u_item_idxs; e.dx = ws + w.dx;
-  if (tem && g_dx_two_partials) e.dx2 = ws + w.dxn;      // the attention backward left d x as two partial rows per position
-  g_dx_two_partials = false;
+  if (enc_take_dx_two_partials()) e.dx2 = ws + w.dxn;   // the attention backward left d x as two partial rows per position
   e.drop_fs = make_drop(D, PS_SITE_FS);
   e.g_hist_tab = ghist; e.g_word_emb = G.word_emb;
   if (D.query_encoder == PS_QENC_FS) {
