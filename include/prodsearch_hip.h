@@ -33,7 +33,13 @@ extern "C" {
 
 typedef void* ps_stream_t; /* hipStream_t */
 
-enum { PS_MODEL_TEM = 0, PS_MODEL_QEM = 1 };
+enum { PS_MODEL_TEM = 0, PS_MODEL_QEM = 1,
+       PS_MODEL_AEM = 2,   /* forward_attn / test_attn, model_name 'AEM': attention over the history only (S = L, L >= 1)     */
+       PS_MODEL_ZAM = 3 }; /* 'ZAM': the same with a zero key / value row prepended, always valid (S = L + 1)                  */
+/* AEM / ZAM (item_transformer.py:148-195, 361-438): attention_encoder.* (neural.py:86-96) travels in PsTemTensors.layer[0]'s
+ * wk..bo (params and grads); its FFN / LayerNorm pointers, pe and the final LayerNorm are not read (NULL).  n_layers and F are
+ * ignored; H heads with d / H <= 64 and H * S <= 4096.  The attention dropout is site PS_SITE_ATTN(0), element
+ * (row = (b R + j) H + h, col = original key index s, ZAM's zero column s = 0) with R = K + 1 replicas when dropout is drawn. */
 enum { PS_QENC_FS = 0, PS_QENC_AVG = 1 };
 
 /* Shape/flag descriptor of one step.  Field <- reference flag (main.py:26-137). */
@@ -50,7 +56,7 @@ typedef struct PsTemDesc {
   int32_t n_layers;      /* --inter_layers                                               */
   int64_t product_size;  /* P; pad index = P, tables have P+1 rows (item_transformer.py:34,46) */
   int64_t vocab_size;    /* V; pad index = V-1                    (item_transformer.py:35)     */
-  int32_t model;         /* PS_MODEL_TEM: forward_dotproduct; PS_MODEL_QEM: forward_attn/QEM */
+  int32_t model;         /* PS_MODEL_TEM: forward_dotproduct; PS_MODEL_QEM: forward_attn/QEM; PS_MODEL_AEM / _ZAM: forward_attn */
   int32_t query_encoder; /* PS_QENC_FS / PS_QENC_AVG          (--query_encoder_name)     */
   int32_t use_pos_emb;   /* --use_pos_emb                                                */
   int32_t use_item_pos;  /* --use_item_pos : output position -1 instead of 0             */
@@ -108,10 +114,12 @@ typedef struct PsTemBatch {
 typedef struct PsTemWsLayout {
   int64_t total_floats;
   int32_t R;             /* encoder replicas per batch row: K+1 if dropout is drawn, else 1 */
-  int32_t S;             /* L+1 */
+  int32_t S;             /* L+1 (AEM: L) */
   int64_t qmean, query_emb, x;                 /* [B,d],[B,d],[B,S,d]                 */
   int64_t kp, vp, qp, attn, ctx;               /* last layer: [n_in*S,d] x2, [n_in,d].. ; K/V rows of MASKED key positions
-                                                  are not written when the one-layer sq1 path is in use (row-list projection) */
+                                                  are not written when the one-layer sq1 path is in use (row-list projection);
+                                                  AEM / ZAM: K, V [B*S,d], scaled Q [B,d], softmax [B,H,S], ctx [B*R,d], and
+                                                  x = the gathered key rows [B*S,d] */
   int64_t y1, ln1, a1, h1, y2, enc;            /* last layer replica rows              */
   int64_t item_scores, word_scores, loss_parts;/* [B,1+K],[B,W,1+K],[B,2]             */
   int64_t denc, dx;                            /* backward: [B*R,d], [B,S,d]           */

@@ -10,7 +10,7 @@ import os
 from . import build as _build
 
 PS_MAX_LAYERS = 8
-PS_MODEL_TEM, PS_MODEL_QEM = 0, 1
+PS_MODEL_TEM, PS_MODEL_QEM, PS_MODEL_AEM, PS_MODEL_ZAM = 0, 1, 2, 3
 PS_QENC_FS, PS_QENC_AVG = 0, 1
 
 _f32p = C.POINTER(C.c_float)

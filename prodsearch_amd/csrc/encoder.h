@@ -23,6 +23,7 @@ struct Ws {
   int64_t gcpart;           // [4 * row tiles][3][F] parked column sums of the FF2 dX GEMM (b1 gradient)
   int64_t abpart;           // per layer [n_in][3][d] parked attention bias gradients {bq, bk, bv} (sq1 backward)
   int64_t vrows, vcount;    // int32 [B*S] valid-row list of x and its length (EmbedArgs::vrows), TEM only
+  int64_t ae_qhalf, ae_dhalf, ae_dqe, ae_dqp, ae_dk, ae_dv, ae_part, ae_keys;   // AEM / ZAM (attn_emb.hip), 0 otherwise
   int64_t stage;            // graph replay: step word + staged copies of the call's int64 index tensors (stage_layout)
   int64_t total;
 };
@@ -58,10 +59,20 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
 void enc_clear_call_flags();
 bool enc_take_dx_two_partials();
 
+// ZAM / AEM (attn_emb.hip): the attention-embedding step between the query encoder and the scoring.  ae_forward reads
+// w.query_emb and writes w.enc [B*R,d]; ae_backward reads w.denc and leaves d query_emb in w.ae_dqe [B,d].
+#define PS_AE_COL_SPLITS 128      // row splits of ae_backward's deterministic bias column sums (w.ae_part: [4][splits][d])
+bool ps_model_attn(int model);
+int ae_zoff(const PsTemDesc& D);
+int ae_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, float* ws, const Ws& w, hipStream_t st);
+int ae_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui, float* ws, const Ws& w,
+                hipStream_t st);
+
 GemmProblem gp(const float* A, int lda, int ta, const float* Bm, int ldb, int tb, float* C, int ldc, int M, int N, int K);
 int run1(const GemmProblem& p, hipStream_t st);
 GemmProblem gp_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int n_out, int k_in, int rows);
 int side_wgrads(GemmProblem* ps, int n, hipStream_t main_st);
+int main_wgrads(GemmProblem* ps, int n, hipStream_t st);   // the same weight-gradient launch on `st` itself
 int side_fork(hipStream_t main_st);
 int side_run(GemmProblem* ps, int n, hipStream_t main_st);
 int side_join(hipStream_t main_st);

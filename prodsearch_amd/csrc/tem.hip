@@ -100,7 +100,12 @@ static int check_desc(const PsTemDesc& D) {
   PS_REQUIRE(D.B > 0 && D.K >= 0 && D.Q > 0 && D.W >= 0 && D.d > 0, "desc: bad sizes B=%d K=%d Q=%d W=%d d=%d",
              D.B, D.K, D.Q, D.W, D.d);
   PS_REQUIRE(D.d % 32 == 0 && D.d <= 512, "desc: embedding_size %d must be a multiple of 32 and <= 512", D.d);
-  PS_REQUIRE(D.model == PS_MODEL_TEM || D.model == PS_MODEL_QEM, "desc: model %d", D.model);
+  PS_REQUIRE(D.model == PS_MODEL_TEM || D.model == PS_MODEL_QEM || ps_model_attn(D.model), "desc: model %d", D.model);
+  if (ps_model_attn(D.model)) {
+    const int S = D.L + ae_zoff(D);
+    PS_REQUIRE(D.L >= (D.model == PS_MODEL_AEM ? 1 : 0) && S <= 64, "desc: history length %d (AEM: L >= 1, S <= 64)", D.L);
+    PS_REQUIRE(D.H > 0 && D.d % D.H == 0 && D.d / D.H <= 64 && D.H * S <= 4096, "desc: heads %d for d %d", D.H, D.d);
+  }
   if (D.model == PS_MODEL_TEM) {
     PS_REQUIRE(D.L >= 0 && D.L + 1 <= 64, "desc: history length %d (S <= 64)", D.L);
     PS_REQUIRE(D.n_layers >= 0 && D.n_layers <= PS_MAX_LAYERS, "desc: inter_layers %d", D.n_layers);
@@ -124,11 +129,11 @@ int make_ws(const PsTemDesc& D, Ws& w) {
   int rc = check_desc(D);
   if (rc) return rc;
   memset(&w, 0, sizeof(w));
-  const bool tem = D.model == PS_MODEL_TEM;
+  const bool tem = D.model == PS_MODEL_TEM, ae = ps_model_attn(D.model);
   const bool drop = D.training && D.dropout > 0.f;
-  const int B = D.B, d = D.d, S = tem ? D.L + 1 : 1, NL = tem ? D.n_layers : 0;
+  const int B = D.B, d = D.d, S = tem ? D.L + 1 : (ae ? D.L + ae_zoff(D) : 1), NL = tem ? D.n_layers : 0;
   w.S = S;
-  w.R = (tem && drop && NL > 0 && D.C == 0) ? D.K + 1 : 1;
+  w.R = (((tem && NL > 0) || ae) && drop && D.C == 0) ? D.K + 1 : 1;
   w.qpos = D.use_item_pos ? S - 1 : 0;
   int64_t cur = 0;
   w.qmean = take(cur, (int64_t)B * d);
@@ -162,7 +167,28 @@ int make_ws(const PsTemDesc& D, Ws& w) {
   }
   w.Mf = B * w.R;
   w.fin_stats = take(cur, (int64_t)w.Mf * 2);
-  w.enc = tem ? take(cur, (int64_t)w.Mf * d) : w.query_emb;
+  if (ae) {      // AEM / ZAM (attn_emb.hip): key rows, K / V / Q, softmax, per-replica ctx and their gradients
+    LayerWs& l = w.layer[0];
+    const int64_t ns = (int64_t)B * S;
+    l.n_in = B; l.n_out = B * w.R; l.fan = w.R; l.Sq = 1; l.M2 = B * w.R;
+    w.x = take(cur, ns * d);
+    l.kp = take(cur, ns * d);
+    l.vp = take(cur, ns * d);
+    l.qp = take(cur, (int64_t)B * d);
+    l.attn = take(cur, (int64_t)B * D.H * S);
+    l.ctx = take(cur, (int64_t)B * w.R * d);
+    w.ae_qhalf = take(cur, (int64_t)B * d);
+    w.ae_dhalf = take(cur, (int64_t)B * w.R * d);
+    w.dctx = take(cur, (int64_t)B * w.R * d);
+    w.ae_dqe = take(cur, (int64_t)B * d);
+    w.ae_dqp = take(cur, (int64_t)B * d);
+    w.ae_dk = take(cur, ns * d);
+    w.ae_dv = take(cur, ns * d);
+    w.dx = take(cur, ns * d);
+    w.ae_part = take(cur, (int64_t)4 * PS_AE_COL_SPLITS * d);
+    w.ae_keys = take(cur, (int64_t)2 * B * D.L);     // int32 [2][B*L]: deterministic scatter tasks
+  }
+  w.enc = (tem || ae) ? take(cur, (int64_t)w.Mf * d) : w.query_emb;
   const int C = D.C > 0 ? D.C : D.K + 1;
   w.item_scores = take(cur, (int64_t)B * C);
   w.word_scores = take(cur, (int64_t)B * (D.W > 0 ? D.W : 1) * (D.K + 1));
@@ -212,7 +238,7 @@ extern "C" int ps_tem_workspace_layout(const PsTemDesc* desc, PsTemWsLayout* out
   out->total_floats = w.total;
   out->R = w.R; out->S = w.S;
   out->qmean = w.qmean; out->query_emb = w.query_emb; out->x = w.x;
-  const int NL = desc->model == PS_MODEL_TEM ? desc->n_layers : 0;
+  const int NL = desc->model == PS_MODEL_TEM ? desc->n_layers : (ps_model_attn(desc->model) ? 1 : 0);
   if (NL > 0) {
     const LayerWs& l = w.layer[NL - 1];
     out->kp = l.kp; out->vp = l.vp; out->qp = l.qp; out->attn = l.attn; out->ctx = l.ctx;
@@ -364,6 +390,8 @@ static int run_wgrads_det(GemmGroup& g, hipStream_t st) {
 // the last arriver of a tile adds the partials up in split order — deterministic and free of fp32 atomics, but 122 us against
 // 44 for the grouped launch at C2 and 0.395 against 0.292 ms per step: the device-scope release each of the 600 workgroups
 // needs before its ticket writes back its XCD's L2, MI300-class L2s not being coherent with one another)
+static int run_wgrads(GemmProblem* ps, int n, hipStream_t st);
+int main_wgrads(GemmProblem* ps, int n, hipStream_t st) { return run_wgrads(ps, n, st); }
 static int run_wgrads(GemmProblem* ps, int n, hipStream_t st) {
   GemmGroup g;
   memset(&g, 0, sizeof(g));
@@ -925,7 +953,7 @@ static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const 
   e.word_emb = P.word_emb; e.hist_tab = hist; e.pe = P.pe;
   e.drop_fs = make_drop(D, PS_SITE_FS);
   e.qmean_d = ws + w.qmean; e.query_emb = ws + w.query_emb; e.x = ws + w.x;
-  PS_REQUIRE(e.qw && (!tem || e.ui), "forward: null batch indices");
+  PS_REQUIRE(e.qw && ((!tem && !ps_model_attn(D.model)) || e.ui), "forward: null batch indices");
   PS_REQUIRE(!tem || !D.use_pos_emb || P.pe, "forward: null positional table");
   if (tem && rows_list_ok(D)) { e.vrows = reinterpret_cast<int32_t*>(ws + w.vrows); e.vcount = reinterpret_cast<int32_t*>(ws + w.vcount); }
   const float* wp_w[PS_WPLANES_MAX]; int wp_r[PS_WPLANES_MAX], wp_c[PS_WPLANES_MAX];
@@ -952,6 +980,7 @@ static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const 
     if (tem) { p.out2 = ws + w.x; p.ld2 = S * d; p.add2 = D.use_pos_emb ? P.pe : nullptr; }
     TRY(run1(p, st));
   }
+  if (ps_model_attn(D.model)) return ae_forward(D, P, Bt.u_item_idxs, ws, w, st);
   if (!tem) return PS_OK;
 
   return enc_layers_forward(D, P, Bt.u_item_idxs, nullptr, ws, w, st, rows_list_ok(D), fold_sc);
@@ -1499,6 +1528,9 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
     if (rc_enc != PS_OK) { g_wg3_last_n = 0; return rc_enc; }
     dqe = ws + w.dx;      // row 0 of each sequence is the query embedding
     lddqe = S * d;
+  } else if (ps_model_attn(D.model)) {
+    TRY(ae_backward(D, P, G, batch->u_item_idxs, ws, w, st));
+    dqe = ws + w.ae_dqe;
   }
 
   // 4. query encoder backward + scatter to the word / history rows
@@ -1607,7 +1639,8 @@ extern "C" int ps_tem_forward_step(const PsTemDesc* desc, const PsTemTensors* pa
   TRY(make_ws(D, w));
   hipStream_t st = (hipStream_t)stream;
   const bool sampled = sampler_prob && sampler_alias;
-  PS_REQUIRE(batch->query_word_idxs && batch->target_prod_idxs && (D.model != PS_MODEL_TEM || batch->u_item_idxs) &&
+  const bool hist = D.model == PS_MODEL_TEM || ps_model_attn(D.model);
+  PS_REQUIRE(batch->query_word_idxs && batch->target_prod_idxs && (!hist || batch->u_item_idxs) &&
              (D.W == 0 || batch->pos_iword_idxs), "forward_step: null batch tensors");
   PS_REQUIRE(sampled || (batch->neg_item_idxs && (D.W == 0 || batch->neg_word_idxs)), "forward_step: no negatives");
   PS_REQUIRE(params->word_bias && (!D.bias_product || params->product_bias), "forward_step: null bias tensors");
@@ -1615,7 +1648,7 @@ extern "C" int ps_tem_forward_step(const PsTemDesc* desc, const PsTemTensors* pa
   const PsTemBatch Bs = staged_batch(L);
   StageArgs sa;
   memset(&sa, 0, sizeof(sa));
-  const int64_t* src[6] = {batch->query_word_idxs, D.model == PS_MODEL_TEM ? batch->u_item_idxs : nullptr,
+  const int64_t* src[6] = {batch->query_word_idxs, hist ? batch->u_item_idxs : nullptr,
                            batch->target_prod_idxs, D.W > 0 ? batch->pos_iword_idxs : nullptr,
                            sampled ? nullptr : batch->neg_item_idxs, (sampled || D.W == 0) ? nullptr : batch->neg_word_idxs};
   for (int k = 0; k < 6; ++k) { sa.src[k] = src[k]; sa.dst[k] = L.p[k]; sa.n[k] = L.n[k]; }

@@ -15,9 +15,10 @@ each into ``libprodsearch_hip.so`` (hand-written gfx950 kernels); PyTorch owns
 the memory and lends raw pointers for the duration of the call.  There is no
 CPU fallback — on a CPU tensor the model raises.
 
-Supported: ``model_name`` in {item_transformer (with use_dot_prod), QEM}.  The other
-scoring heads of the reference (forward_trans, ZAM/AEM, forward_seq) are outside
-the hot path and raise NotImplementedError.
+Supported: ``model_name`` in {item_transformer (with use_dot_prod), QEM}.  ZAM / AEM run through
+:class:`prodsearch_amd.AttentionEmbeddingRanker` (a subclass, ``attn_embedding.py``); this class refuses them, as it
+refuses the reference's other scoring heads (forward_trans, forward_seq), which are outside the hot path (SURVEY.md §2
+row 13): NotImplementedError.
 """
 import math
 
@@ -168,11 +169,7 @@ class ItemTransformerRanker(nn.Module):
         elif _DET_SET_BY_ARGS:
             _lib.load().ps_set_deterministic(0)
             _DET_SET_BY_ARGS = False
-        if args.model_name not in ('item_transformer', 'QEM'):
-            raise NotImplementedError("model_name %r is outside the hot path (item_transformer/QEM only)"
-                                      % args.model_name)
-        if args.model_name == 'item_transformer' and not args.use_dot_prod:
-            raise NotImplementedError("forward_trans (use_dot_prod=False) is outside the hot path")
+        self._check_model_name(args)
         if getattr(args, 'pretrain_emb_dir', '') or getattr(args, 'pretrain_up_emb_dir', ''):
             raise NotImplementedError("pretrained-embedding text loaders are out of scope; load a state_dict")
         self.args = args
@@ -239,6 +236,21 @@ class ItemTransformerRanker(nn.Module):
         self._alias = None
         self._fwd_step = 0
         self._seed = int(getattr(args, 'seed', 666))
+
+    # ------------------------------------------------------------ model-kind hooks (AttentionEmbeddingRanker overrides them)
+    def _check_model_name(self, args):
+        if args.model_name not in ('item_transformer', 'QEM'):
+            raise NotImplementedError("model_name %r is outside the hot path (item_transformer/QEM only)"
+                                      % args.model_name)
+        if args.model_name == 'item_transformer' and not args.use_dot_prod:
+            raise NotImplementedError("forward_trans (use_dot_prod=False) is outside the hot path")
+
+    def _model_id(self):
+        return _lib.PS_MODEL_TEM if self.args.model_name == 'item_transformer' else _lib.PS_MODEL_QEM
+
+    def _uses_history(self):
+        """Does the step read ``u_item_idxs`` rows of the history table?"""
+        return self.args.model_name == 'item_transformer'
 
     # ---------------------------------------------------------------- reference API
     def initialize_parameters(self, logger=None):
@@ -476,7 +488,7 @@ class ItemTransformerRanker(nn.Module):
             d.d, d.H, d.F = a.embedding_size, a.heads, a.ff_size
             d.n_layers = a.inter_layers if a.model_name == 'item_transformer' else 0
             d.product_size, d.vocab_size = (self._shard.slots if self._shard is not None else self.product_size), self.vocab_size
-            d.model = _lib.PS_MODEL_TEM if a.model_name == 'item_transformer' else _lib.PS_MODEL_QEM
+            d.model = self._model_id()
             d.query_encoder = _lib.PS_QENC_FS if a.query_encoder_name == 'fs' else _lib.PS_QENC_AVG
             d.use_pos_emb, d.use_item_pos = int(a.use_pos_emb), int(a.use_item_pos)
             d.bias_product = int(a.sim_func == 'bias_product')
@@ -696,7 +708,7 @@ class ItemTransformerRanker(nn.Module):
         """Index tensors of the step that address ``path``'s rows, and that table's pad row."""
         tg, pw, ni, nw = plan.keep[2:6]
         qw, ui = plan.keep[0], plan.keep[1]
-        tem = self.args.model_name == 'item_transformer'
+        tem = self._uses_history()
         if path == ('product_emb',):
             return [tg, ni] + ([ui] if tem and not self.args.sep_prod_emb else []), self.prod_pad_idx
         if path == ('hist_product_emb',):
@@ -712,7 +724,7 @@ class ItemTransformerRanker(nn.Module):
         if plan is None:
             return 1
         d, a = plan.desc, self.args
-        tem = a.model_name == 'item_transformer'
+        tem = self._uses_history()
         Lmax = max(int(d.L), int(getattr(a, 'uprev_review_limit', d.L)))
         if path == ('product_emb',):
             return d.B * (1 + d.K + (Lmax if tem and not a.sep_prod_emb else 0))

@@ -21,6 +21,7 @@ import torch
 
 from . import corpus, evaluate, pyrandom
 from .dataloader import ItemPVDataloader
+from .attn_embedding import AttentionEmbeddingRanker
 from .item_transformer import ItemTransformerRanker
 from .optimizers import build_optim
 from .ps_model import ProductRanker
@@ -38,6 +39,9 @@ def create_model(args, global_data, prod_data, load_path=''):
     elif args.model_name in ('item_transformer', 'QEM'):
         model = ItemTransformerRanker(args, args.device, global_data.vocab_size, global_data.product_size,
                                       global_data.words, word_dists=prod_data.word_dists)
+    elif args.model_name in AttentionEmbeddingRanker.MODEL_NAMES:
+        model = AttentionEmbeddingRanker(args, args.device, global_data.vocab_size, global_data.product_size,
+                                         global_data.words, word_dists=prod_data.word_dists)
     else:
         raise NotImplementedError("trainer: model_name %r is not built (SURVEY.md §8)" % args.model_name)
     if load_path and os.path.exists(load_path):
