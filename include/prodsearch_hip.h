@@ -84,7 +84,10 @@ typedef struct PsLayerTensors {
 
 /* A full set of model tensors.  The same struct describes parameters, their
  * gradients, and Adam moments (pointers may be NULL where the reference has no
- * gradient: product_bias unless bias_product, layer-0 ln, hist table unless sep). */
+ * gradient: product_bias unless bias_product, layer-0 ln, hist table unless sep).
+ * As a gradient struct of ps_tem_backward / ps_tem_backward_step, word_emb NULL means
+ * the word table is FROZEN (pretrain_emb_dir: nn.Embedding.from_pretrained, freeze=True):
+ * no word-row gradient is read or written; word_bias and the other tables stay required. */
 typedef struct PsTemTensors {
   float *product_emb;       /* product_emb.weight      [P+1, d] (item_transformer.py:46) */
   float *hist_product_emb;  /* hist_product_emb.weight [P+1, d] (:48) or NULL            */

@@ -1278,7 +1278,9 @@ int launch_loss(const ScoreArgs& a, hipStream_t st) {
 // atomics, with pad rows adding 0.f to a real address instead of branching — a load or an atomic under a per-group condition
 // (the `k < epl` form this replaces) made the compiler wait for everything in flight at every join, i.e. for the previous
 // group's ATOMICS to be acknowledged before the next group's loads were even issued: four dependent round trips per task.
-template <int EPL>
+// WG = false: the word table is frozen (g_word_emb null) — the word tasks keep their dot products (the target
+// item's gradient) and the word_bias atomics, and neither read the target item's row for nor add into a word-gradient row.
+template <int EPL, bool WG = true>
 __global__ __launch_bounds__(32 * SB_RG) void score_bwd_kernel(const ScoreArgs a) {
   extern __shared__ float red[];                 // [SB_RG][d]
   const int tid = threadIdx.x, rg = tid >> 5, c = tid & 31;
@@ -1361,8 +1363,10 @@ __global__ __launch_bounds__(32 * SB_RG) void score_bwd_kernel(const ScoreArgs a
   const float cf = invB / (float)(cnt > 0 ? cnt : 1);
   const float* prow = a.product_emb + (size_t)tb * d;
   float pv[EPL];
+  if (WG) {
 #pragma unroll
-  for (int k = 0; k < EPL; ++k) pv[k] = prow[col[k]];
+    for (int k = 0; k < EPL; ++k) pv[k] = prow[col[k]];
+  }
   for (int t = wt0; t < a.W * K1; t += wstride) {
     const int w = t / K1, j = t - w * K1;
     const int64_t pw = a.pos_words[(size_t)b * a.W + w];
@@ -1371,14 +1375,14 @@ __global__ __launch_bounds__(32 * SB_RG) void score_bwd_kernel(const ScoreArgs a
     const float s = a.word_scores[((size_t)b * a.W + w) * K1 + j];
     const float ds = (j == 0 ? sigmoid_f(s) - 1.f : sigmoid_f(s)) * cf;
     const float* wrow = a.word_emb + (size_t)idx * d;
-    float* grow = a.g_word_emb + (size_t)idx * d;
+    float* grow = WG ? a.g_word_emb + (size_t)idx * d : nullptr;
     float wv[EPL];
 #pragma unroll
     for (int k = 0; k < EPL; ++k) wv[k] = wrow[col[k]];
     const bool live = idx != a.V - 1;
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
-      if (EPL < 16 || cok[k]) atomicAdd(&grow[col[k]], live ? ds * pv[k] : 0.f);
+      if (WG && (EPL < 16 || cok[k])) atomicAdd(&grow[col[k]], live ? ds * pv[k] : 0.f);
       acc[k] += ds * wv[k];
     }
     if (c == 0) atomicAdd(&a.g_word_bias[idx], ds);
@@ -1396,13 +1400,18 @@ __global__ __launch_bounds__(32 * SB_RG) void score_bwd_kernel(const ScoreArgs a
     }
   GS_STAMP(3);
 }
-static void launch_score_bwd_kernel(const ScoreArgs& a, int blocks, hipStream_t st) {
+template <bool WG>
+static void launch_score_bwd_kernel_wg(const ScoreArgs& a, int blocks, hipStream_t st) {
   const size_t lds = (size_t)SB_RG * a.d * sizeof(float);
-  if (a.d == 32) hipLaunchKernelGGL(score_bwd_kernel<1>, dim3(blocks), dim3(32 * SB_RG), lds, st, a);
-  else if (a.d == 64) hipLaunchKernelGGL(score_bwd_kernel<2>, dim3(blocks), dim3(32 * SB_RG), lds, st, a);
-  else if (a.d == 128) hipLaunchKernelGGL(score_bwd_kernel<4>, dim3(blocks), dim3(32 * SB_RG), lds, st, a);
-  else if (a.d == 256) hipLaunchKernelGGL(score_bwd_kernel<8>, dim3(blocks), dim3(32 * SB_RG), lds, st, a);
-  else hipLaunchKernelGGL(score_bwd_kernel<16>, dim3(blocks), dim3(32 * SB_RG), lds, st, a);
+  if (a.d == 32) hipLaunchKernelGGL((score_bwd_kernel<1, WG>), dim3(blocks), dim3(32 * SB_RG), lds, st, a);
+  else if (a.d == 64) hipLaunchKernelGGL((score_bwd_kernel<2, WG>), dim3(blocks), dim3(32 * SB_RG), lds, st, a);
+  else if (a.d == 128) hipLaunchKernelGGL((score_bwd_kernel<4, WG>), dim3(blocks), dim3(32 * SB_RG), lds, st, a);
+  else if (a.d == 256) hipLaunchKernelGGL((score_bwd_kernel<8, WG>), dim3(blocks), dim3(32 * SB_RG), lds, st, a);
+  else hipLaunchKernelGGL((score_bwd_kernel<16, WG>), dim3(blocks), dim3(32 * SB_RG), lds, st, a);
+}
+static void launch_score_bwd_kernel(const ScoreArgs& a, int blocks, hipStream_t st) {
+  if (a.g_word_emb) launch_score_bwd_kernel_wg<true>(a, blocks, st);
+  else launch_score_bwd_kernel_wg<false>(a, blocks, st);
 }
 
 // Deterministic form of the table scatter above (ps_deterministic): every gradient row has ONE owner — half-wave
@@ -1417,7 +1426,8 @@ template <int EPL> struct DetItemT { float v[EPL]; float bias; int64_t row; };  
 // fetch(t, item) fills the contribution of task t; the walk adds it to table[row] (skipped for row == skip_row) and to
 // bias[row] (if given).  Consecutive matches of one row are summed in registers first (in task order) — a popular row's
 // chain is then one atomic per up to DW_B tasks.
-template <int EPL, class FetchF>
+// TABLE = false: only the bias entries are added (a frozen table: `table` is never touched).
+template <int EPL, bool TABLE = true, class FetchF>
 __device__ inline void det_owner_walk(int ntask, int owner, int nown, int hl, int d, float* table, float* bias, int64_t skip_row,
                                       const int32_t* keys, FetchF fetch) {
   // A round = DW_U chunks of 32 tasks: all their keys are requested together, lane u of the half-wave keeps the match
@@ -1465,7 +1475,7 @@ __device__ inline void det_owner_walk(int ntask, int owner, int nown, int hl, in
         const bool have = q < n;
         const int64_t row = have ? it[q < DW_B ? q : 0].row : -2;
         if (cur >= 0 && row != cur) {                          // flush the finished run (half-wave uniform)
-          if (cur != skip_row) {
+          if (TABLE && cur != skip_row) {
             float* dst = table + (size_t)cur * d;
 #pragma unroll
             for (int k = 0; k < EPL; ++k)
@@ -1548,7 +1558,7 @@ __global__ __launch_bounds__(256) void score_bwd_det_pre_kernel(const ScoreArgs 
   for (int k = 0; k < BW_MAXE; ++k)
     if (k < epl) term[(size_t)b * d + c + 32 * k] = v[k];
 }
-template <int EPL>
+template <int EPL, bool WG = true>      // WG = false: frozen word table, the word walk adds the word_bias entries only
 __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void score_bwd_det_kernel(const ScoreArgs a, const float* term, const int32_t* keys) {
   typedef DetItemT<EPL> DetItem;
   const int tid = threadIdx.x, hl = tid & 31, c = hl;
@@ -1582,7 +1592,7 @@ __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void score_bwd_det_kernel(c
       it.bias = 0.f;
     });
   // ---- ... and the word rows
-  det_owner_walk<EPL>(a.B * a.W * K1, owner, nown, hl, d, a.g_word_emb, a.g_word_bias, a.V - 1, keys_word,
+  det_owner_walk<EPL, WG>(a.B * a.W * K1, owner, nown, hl, d, a.g_word_emb, a.g_word_bias, a.V - 1, keys_word,
     [&](int u, DetItem& it) {
       const int b = fdiv(u, a.fWK1), r = u - b * a.W * K1, w = r / K1, j = r - w * K1;
       it.row = keys_word[u];
@@ -1590,7 +1600,7 @@ __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void score_bwd_det_kernel(c
       const float* prow = a.product_emb + (size_t)clamp_idx(a.target[b], a.P) * d;
       float pv[EPL];
 #pragma unroll
-      for (int k = 0; k < EPL; ++k) pv[k] = k < epl ? prow[c + 32 * k] : 0.f;
+      for (int k = 0; k < EPL; ++k) pv[k] = (WG && k < epl) ? prow[c + 32 * k] : 0.f;
       int cnt = 0;
       for (int w2 = 0; w2 < a.W; ++w2) cnt += (a.pos_words[(size_t)b * a.W + w2] != a.V - 1);
       const float ds = (j == 0 ? sigmoid_f(s) - 1.f : sigmoid_f(s)) * (invB / (float)(cnt > 0 ? cnt : 1));
@@ -1619,9 +1629,15 @@ int launch_score_bwd(const ScoreArgs& a, hipStream_t st) {
       int32_t* keys = reinterpret_cast<int32_t*>(term + (size_t)a.B * a.d);
       hipLaunchKernelGGL(score_bwd_det_pre_kernel, dim3(ps_cdiv(a.B, 8)), dim3(256), 0, st, a, term, keys);
       PS_LAUNCH_CHECK();
-      if (a.d <= 128) hipLaunchKernelGGL(score_bwd_det_kernel<4>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
-      else if (a.d <= 256) hipLaunchKernelGGL(score_bwd_det_kernel<8>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
-      else hipLaunchKernelGGL(score_bwd_det_kernel<16>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+      if (a.g_word_emb) {
+        if (a.d <= 128) hipLaunchKernelGGL(score_bwd_det_kernel<4>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+        else if (a.d <= 256) hipLaunchKernelGGL(score_bwd_det_kernel<8>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+        else hipLaunchKernelGGL(score_bwd_det_kernel<16>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+      } else {
+        if (a.d <= 128) hipLaunchKernelGGL((score_bwd_det_kernel<4, false>), dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+        else if (a.d <= 256) hipLaunchKernelGGL((score_bwd_det_kernel<8, false>), dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+        else hipLaunchKernelGGL((score_bwd_det_kernel<16, false>), dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a, term, keys);
+      }
       PS_LAUNCH_CHECK();
     }
     return PS_OK;
@@ -1657,6 +1673,9 @@ __device__ __forceinline__ void row_fetch_add2(float* dst, const float* src, con
 }
 // Backward of the history gather (item_transformer.py:466-469) and of the query mean
 // (text_encoder.py:6-16 + FS dropout): dense grads with padding_idx rows untouched.
+// WG = false: the word table is frozen (g_word_emb null): the FS row workgroups stop after dqpre and the bias gradient (the
+// d mean they would go on to build has no consumer), and the launcher hands no query-word tasks.
+template <bool WG>
 __global__ __launch_bounds__(256) void embed_scatter_kernel(const EmbedBwdArgs a, int ntask, int nq, int nfw, int nfold) {
   fork_signal(a.sig, a.sigval);
   extern __shared__ float fsb_s[];               // fused FS backward only: [d] dqpre, [rpp][d] partials, [d] d mean
@@ -1671,7 +1690,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const EmbedBwdArgs a
     float* dq_s = fsb_s;
     float* part_s = fsb_s + d;
     float* dm_s = part_s + (size_t)rpp * d;
-    const bool pre = d == 128;                    // weight rows o = rg + 8u fetched up front, under the dqpre round trip
+    const bool pre = WG && d == 128;              // weight rows o = rg + 8u fetched up front, under the dqpre round trip
     float4 wq[16];
     if (pre) {
 #pragma unroll
@@ -1686,6 +1705,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const EmbedBwdArgs a
         atomicAdd(&a.g_fs_b[e], v);
       }
     }
+    if (!WG) return;                               // (kernel-uniform)
     int cnt = 0;
     if (a.Q <= 64) {      // one load per lane and a ballot (as a loop: Q loads, each waited for — DESIGN.md 5f, loops)
       const int ql = tid & 63;
@@ -1832,6 +1852,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const EmbedBwdArgs a
       default: for (int k = 0; k < epl; ++k) atomicAdd(&dst[c + 32 * k], src[c + 32 * k]);
     }
   } else {
+    if (!WG) return;                              // (no such tasks are launched)
     int u = t - nitem;
     int b = u / a.Q;
     int64_t idx = a.qw[u];
@@ -1875,7 +1896,7 @@ __global__ __launch_bounds__(256) void embed_scatter_det_keys_kernel(const Embed
   for (int t = g; t < nh; t += gn) { const int64_t idx = a.ui[t]; keys[t] = (idx == a.P || idx < 0 || idx > a.P) ? -1 : (int32_t)idx; }
   for (int u = g; u < a.B * a.Q; u += gn) { const int64_t idx = a.qw[u]; keys[nh + u] = (idx == a.V - 1 || idx < 0 || idx >= a.V) ? -1 : (int32_t)idx; }
 }
-template <int EPL>
+template <int EPL, bool WG = true>      // WG = false: frozen word table, the history rows only
 __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void embed_scatter_det_kernel(const EmbedBwdArgs a, const int32_t* keys) {
   typedef DetItemT<EPL> DetItem;
   const int nh = a.tem ? a.B * a.L : 0;
@@ -1892,7 +1913,7 @@ __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void embed_scatter_det_kern
         for (int k = 0; k < EPL; ++k) it.v[k] = k < epl ? src[c + 32 * k] : 0.f;
         it.bias = 0.f;
       });
-  det_owner_walk<EPL>(a.B * a.Q, owner, nown, hl, d, a.g_word_emb, nullptr, -1, keys + nh,
+  if (WG) det_owner_walk<EPL>(a.B * a.Q, owner, nown, hl, d, a.g_word_emb, nullptr, -1, keys + nh,
     [&](int u, DetItem& it) {
       const int b = u / a.Q;
       it.row = keys[nh + u];
@@ -1951,14 +1972,17 @@ int launch_embed_scatter(const EmbedBwdArgs& a, hipStream_t st) {
   PS_REQUIRE(!fsb || (a.fsb_dqe && a.fsb_qe && a.g_fs_b && a.g_fs_w && a.fw_x && a.d <= 1024),
              "embed scatter: fused FS backward operands missing");
   const bool det = ps_deterministic();
-  PS_REQUIRE(!det || !fsb || a.det_dm, "embed scatter: deterministic mode needs the d-mean buffer");
+  const bool wg = a.g_word_emb != nullptr;                      // null: frozen word table, no query-word rows
+  PS_REQUIRE(!wg || fsb || a.dqmean_d, "embed scatter: the query-word rows need d mean (dqmean_d)");
+  PS_REQUIRE(!det || !fsb || !wg || a.det_dm, "embed scatter: deterministic mode needs the d-mean buffer");
   PS_REQUIRE(!det || a.d <= 32 * BW_MAXE, "embed scatter: deterministic mode supports d <= %d", 32 * BW_MAXE);
-  int ntask = (a.tem ? a.B * a.L : 0) + (fsb ? 0 : a.B * a.Q);   // fused: the query words are scattered by the row workgroups
+  int ntask = (a.tem ? a.B * a.L : 0) + (fsb || !wg ? 0 : a.B * a.Q);   // fused: the query words are scattered by the row workgroups
   if (det) ntask = 0;                                            // ... deterministic mode: by the sole-owner pass below
   static const int parts = ps_diag_int("PS_SCATTER_PARTS", 15);   // timing experiments (WRONG results): 1 FS rows, 2 f_W gradient, 4 folds, 8 scatter tasks
   if (!(parts & 8)) ntask = 0;
   const int nsb = ps_cdiv(ntask, 8);
-  const int nq = fsb && (parts & 1) ? a.B : 0;
+  // (frozen: the row workgroups are needed only to leave dqpre for the f_W gradient GEMM)
+  const int nq = fsb && (parts & 1) && (wg || a.fsb_dqpre_out) ? a.B : 0;
   const int nfw = a.g_fs_w && (parts & 2) && !(fsb && a.fsb_dqpre_out) ? ps_cdiv(a.d * a.d, 32) : 0;
   PS_REQUIRE(!a.g_fs_w || fsb || (a.fw_dy && a.fw_x), "embed scatter: f_W gradient operands missing");
   int nfold = 0;
@@ -1976,18 +2000,25 @@ int launch_embed_scatter(const EmbedBwdArgs& a, hipStream_t st) {
   }
   if (nq + nsb + nfw + nfold > 0) {
     side_take_signal(st, &a2.sig, &a2.sigval);        // (every check is behind us: the launch happens)
-    hipLaunchKernelGGL(embed_scatter_kernel, dim3(nq + nsb + nfw + nfold), dim3(256), lds, st, a2, ntask, nq, nfw, nfold);
+    if (wg) hipLaunchKernelGGL(embed_scatter_kernel<true>, dim3(nq + nsb + nfw + nfold), dim3(256), lds, st, a2, ntask, nq, nfw, nfold);
+    else hipLaunchKernelGGL(embed_scatter_kernel<false>, dim3(nq + nsb + nfw + nfold), dim3(256), lds, st, a2, ntask, nq, nfw, nfold);
     PS_LAUNCH_CHECK();
   }
-  if (det) {
+  if (det && (wg || a.tem)) {
     const size_t nkeys = (size_t)a.B * ((a.tem ? a.L : 0) + a.Q);
     int32_t* keys = reinterpret_cast<int32_t*>(ps_det_scratch(1, nkeys + 4, st));   // (the score backward's use of the slot is over)
     PS_REQUIRE(keys, "embed scatter: deterministic mode has no scratch (allocation failed or stream capture)");
     hipLaunchKernelGGL(embed_scatter_det_keys_kernel, dim3(ps_cdiv((int64_t)nkeys, 1024)), dim3(256), 0, st, a2, keys);
     PS_LAUNCH_CHECK();
-    if (a.d <= 128) hipLaunchKernelGGL(embed_scatter_det_kernel<4>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
-    else if (a.d <= 256) hipLaunchKernelGGL(embed_scatter_det_kernel<8>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
-    else hipLaunchKernelGGL(embed_scatter_det_kernel<16>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+    if (wg) {
+      if (a.d <= 128) hipLaunchKernelGGL(embed_scatter_det_kernel<4>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+      else if (a.d <= 256) hipLaunchKernelGGL(embed_scatter_det_kernel<8>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+      else hipLaunchKernelGGL(embed_scatter_det_kernel<16>, dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+    } else {
+      if (a.d <= 128) hipLaunchKernelGGL((embed_scatter_det_kernel<4, false>), dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+      else if (a.d <= 256) hipLaunchKernelGGL((embed_scatter_det_kernel<8, false>), dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+      else hipLaunchKernelGGL((embed_scatter_det_kernel<16, false>), dim3(256), dim3(32 * SBD_OWNERS_PER_WG), 0, st, a2, keys);
+    }
     PS_LAUNCH_CHECK();
   }
   return PS_OK;

@@ -1499,7 +1499,10 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   const int B = D.B, d = D.d, S = w.S, NL = tem ? D.n_layers : 0, F = D.F;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
   float* ghist = D.sep_prod_emb ? G.hist_product_emb : G.product_emb;
-  PS_REQUIRE(G.product_emb && G.word_emb && G.word_bias && ghist && hist, "backward: null table gradient");
+  // G.word_emb null: the word table is frozen (a pretrained table, nn.Embedding.from_pretrained): no kernel reads or writes a
+  // word-row gradient, and the d mean of the query encoder (its only consumer) is not built
+  const bool word_grad = G.word_emb != nullptr;
+  PS_REQUIRE(G.product_emb && G.word_bias && ghist && hist, "backward: null table gradient");
   PS_REQUIRE(!D.bias_product || G.product_bias, "backward: null product_bias gradient");
 
   // 1. loss + score backward: d enc, table-row scatter-adds
@@ -1548,7 +1551,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
     if (ps_fusion_enabled() && d <= 128) {
       // ... and so does the rest of the FS backward: tanh', d mean = dqpre . f_W (per-row mat-vec), bias gradient
       e.fsb_dqe = dqe; e.fsb_lddqe = lddqe; e.fsb_qe = ws + w.query_emb; e.fsb_w = P.fs_w; e.g_fs_b = G.fs_b;
-      e.det_dm = ws + w.dqmean;                   // (deterministic mode only: launch_embed_scatter)
+      if (word_grad) e.det_dm = ws + w.dqmean;    // (deterministic mode only: launch_embed_scatter)
       // round 5: the f_W weight gradient as one more member of the weight-gradient GEMM launched behind this one, instead of 512
       // extra workgroups of the scatter launch looping over the batch (33 of its 40 us at C2: tools/scatter_parts.sh); the row
       // workgroups leave dqpre in the workspace for it and add the bias gradient themselves.  PS_FW_BY_GEMM=0: the riders.
@@ -1556,14 +1559,16 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
       if (fw_gemm_on && !ps_deterministic()) { e.fsb_dqpre_out = ws + w.dqpre; fw_by_gemm = true; }
     } else {
       TRY(launch_tanh_bwd(dqe, lddqe, ws + w.query_emb, ws + w.dqpre, G.fs_b, B, d, st));
-      GemmProblem p = gp(ws + w.dqpre, d, 0, P.fs_w, d, 1, ws + w.dqmean, d, B, d, d);   // d mean = dqpre . f_W
-      p.no_deep = 1;   // the tail of the main stream, beside the side stream's weight gradients: the 128-deep form's 133 KB of LDS per
-                       // workgroup waits for whole CUs there (50 us for 0.13 GFLOP at the C5 shard, r04_c5_step_timeline.txt)
-      TRY(run1(p, st));
-      e.dqmean_d = ws + w.dqmean;
+      if (word_grad) {
+        GemmProblem p = gp(ws + w.dqpre, d, 0, P.fs_w, d, 1, ws + w.dqmean, d, B, d, d);   // d mean = dqpre . f_W
+        p.no_deep = 1;   // the tail of the main stream, beside the side stream's weight gradients: the 128-deep form's 133 KB of LDS per
+                         // workgroup waits for whole CUs there (50 us for 0.13 GFLOP at the C5 shard, r04_c5_step_timeline.txt)
+        TRY(run1(p, st));
+        e.dqmean_d = ws + w.dqmean;
+      }
       e.fw_dy = ws + w.dqpre;
     }
-  } else {
+  } else if (word_grad) {
     // AVG encoder: query_emb == post-dropout mean; copy rows to a dense [B,d] buffer
     PS_CHECK_HIP(hipMemcpy2DAsync(ws + w.dqmean, sizeof(float) * d, dqe, sizeof(float) * lddqe, sizeof(float) * d, B,
                                   hipMemcpyDeviceToDevice, st));

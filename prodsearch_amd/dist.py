@@ -136,6 +136,7 @@ class SparseGradExchange(object):
     all 7 links busy where a ring all-reduce of a table-sized buffer would be bound by one."""
 
     def __init__(self, model, optim=None, group=None):
+        _refuse_frozen_words(model)
         self.model = model
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -217,11 +218,19 @@ class SparseGradExchange(object):
         return None
 
 
+def _refuse_frozen_words(model):
+    """Data parallelism with a frozen word table (pretrain_emb_dir / requires_grad False) is not built: refused up front."""
+    w = getattr(model, 'word_embeddings', None)
+    if w is not None and not w.weight.requires_grad:
+        raise NotImplementedError("data-parallel training with a frozen word table (pretrain_emb_dir) is not supported")
+
+
 def flatten_parameters(model, multiple=4):
     """Re-home every graded hot-path parameter of ``model`` into ONE flat fp32 buffer laid out exactly like the model's
     flat gradient buffer (small tensors first, tables last, 16-byte aligned slices, total length a multiple of
     ``multiple``).  The parameters stay ordinary ``nn.Parameter``s with the reference's names — only their storage
     moves — and the C-ABI tensor table is refreshed.  Returns the flat parameter buffer."""
+    _refuse_frozen_words(model)
     model.__dict__['_flat_pad_to'] = int(multiple)
     for p in model.parameters():
         p.grad = None
@@ -507,6 +516,7 @@ def make_exchange(model, optim=None, group=None, mode=None):
     """The exchange matching the model's optimizer mode.  Dense mode: ``sharded`` (reduce-scatter -> owner clip+Adam ->
     all-gather, the default when there is more than one rank and an optimizer to shard) or ``allreduce`` (one flat
     all-reduce, every rank runs the whole optimizer; PS_DP_EXCHANGE=allreduce or ``mode=``)."""
+    _refuse_frozen_words(model)
     if getattr(model, '_row_sparse', lambda: False)():
         return SparseGradExchange(model, optim, group)
     mode = mode or os.environ.get('PS_DP_EXCHANGE') or 'sharded'

@@ -21,6 +21,7 @@ refuses the reference's other scoring heads (forward_trans, forward_seq), which 
 row 13): NotImplementedError.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -170,8 +171,16 @@ class ItemTransformerRanker(nn.Module):
             _lib.load().ps_set_deterministic(0)
             _DET_SET_BY_ARGS = False
         self._check_model_name(args)
-        if getattr(args, 'pretrain_emb_dir', '') or getattr(args, 'pretrain_up_emb_dir', ''):
-            raise NotImplementedError("pretrained-embedding text loaders are out of scope; load a state_dict")
+        # pretrain_emb_dir (item_transformer.py:38-43): taken only if the path exists, else the table trains from scratch.
+        # pretrain_up_emb_dir is accepted and has no effect, as in the reference (its reader sits in a string literal, :50-55).
+        self.pretrain_emb_dir = None
+        if os.path.exists(getattr(args, 'pretrain_emb_dir', '') or ''):
+            self.pretrain_emb_dir = args.pretrain_emb_dir
+        self.pretrain_up_emb_dir = None
+        if os.path.exists(getattr(args, 'pretrain_up_emb_dir', '') or ''):
+            self.pretrain_up_emb_dir = args.pretrain_up_emb_dir
+        if self.pretrain_emb_dir is not None and getattr(args, 'shard_tables', False):
+            raise NotImplementedError("pretrain_emb_dir (a frozen word table) is not supported with shard_tables")
         self.args = args
         self.device = device
         self.train_review_only = args.train_review_only
@@ -211,7 +220,13 @@ class ItemTransformerRanker(nn.Module):
             self.hist_product_emb = nn.Embedding(product_size + 1, d, padding_idx=self.prod_pad_idx, device=emb_dev)
         self.product_bias = nn.Parameter(torch.zeros(product_size + 1), requires_grad=True)
         self.word_bias = nn.Parameter(torch.zeros(vocab_size), requires_grad=True)
-        self.word_embeddings = nn.Embedding(vocab_size, d, padding_idx=self.word_pad_idx)
+        if self.pretrain_emb_dir is not None:
+            # nn.Embedding.from_pretrained (item_transformer.py:59-67): freeze=True, the pad row keeps its file values
+            from .pretrained import word_table
+            table = word_table(self.pretrain_emb_dir, vocab_words, vocab_size, d)
+            self.word_embeddings = nn.Embedding.from_pretrained(torch.from_numpy(table), padding_idx=self.word_pad_idx)
+        else:
+            self.word_embeddings = nn.Embedding(vocab_size, d, padding_idx=self.word_pad_idx)
         if args.model_name == 'item_transformer':
             self.transformer_encoder = _TransformerEncoder(d, args.ff_size, args.inter_layers)
         else:
@@ -254,8 +269,9 @@ class ItemTransformerRanker(nn.Module):
 
     # ---------------------------------------------------------------- reference API
     def initialize_parameters(self, logger=None):
-        """item_transformer.py:576-586."""
-        nn.init.normal_(self.word_embeddings.weight)
+        """item_transformer.py:576-586 (a pretrained word table keeps its values)."""
+        if self.pretrain_emb_dir is None:
+            nn.init.normal_(self.word_embeddings.weight)
         nn.init.normal_(self.seg_embeddings.weight)
         if self.args.query_encoder_name == 'fs':
             _init_like_reference(self.query_encoder)
@@ -405,6 +421,8 @@ class ItemTransformerRanker(nn.Module):
         pre-LN, seg_embeddings, wo)."""
         if path == ('product_bias',):
             return self.args.sim_func == 'bias_product'
+        if path == ('word_emb',):           # frozen (pretrain_emb_dir, or a caller's requires_grad_(False)): NULL gradient
+            return self.word_embeddings.weight.requires_grad
         if path[0] == 'layer' and path[2] in ('ln_g', 'ln_b'):
             return path[1] != 0
         return True
@@ -418,7 +436,9 @@ class ItemTransformerRanker(nn.Module):
 
     def _structs(self):
         if self._params_struct is not None:
-            return self._params_struct, self._grads_struct
+            if self.__dict__.get('_word_grad_at') == self.word_embeddings.weight.requires_grad:
+                return self._params_struct, self._grads_struct
+            self._regrade()
         dev = self._dev()
         hot = self._named_hot_params()
         for _, p in hot:
@@ -455,8 +475,30 @@ class ItemTransformerRanker(nn.Module):
         self._n_allreduce_grad = self._n_dense_grad - ((self.product_emb.weight.numel() + 3) // 4 * 4 if self._shard is not None else 0)
         self._sparse_tabs = [(path, p, v) for (path, p), (_, v) in zip(graded, self._grad_views) if path in sparse]
         self._params_struct, self._grads_struct = ps, gs
+        self.__dict__['_word_grad_at'] = self.word_embeddings.weight.requires_grad
         self._loss_acc = torch.zeros(2, device=dev, dtype=torch.float32)
         return ps, gs
+
+    def _regrade(self):
+        """``word_embeddings.weight.requires_grad`` changed since the structs were built: the gradient struct, the flat
+        gradient buffer and its views are rebuilt by the caller (_structs), so a frozen table never receives a gradient and a
+        trainable one never loses it.  The gradients of the previous layout are dropped (``.grad = None``, as after
+        ``zero_grad()``); the optimizer re-plans on the new ``.grad`` tensors, keeping its moments, and a graph-replayed backward is captured again (its key holds the gradient pointers).  The
+        data-parallel forms (flat parameter buffer) and lazy_exact_adam (rows replayed against the table's history) refuse."""
+        if self.__dict__.get('_param_flat') is not None or self._lazy_exact():
+            raise RuntimeError("word_embeddings.weight.requires_grad changed after the first step: not supported with %s"
+                               % ("lazy_exact_adam" if self._lazy_exact() else "a data-parallel exchange"))
+        for p, v in self._grad_views or ():
+            if p.grad is not None:
+                if p.grad is not v and p.grad.data_ptr() != v.data_ptr():
+                    raise RuntimeError("a foreign .grad tensor is attached to a hot-path parameter; "
+                                       "call model.zero_grad() before backward")
+                p.grad = None
+        self.__dict__['_grad_clean'] = False
+        self._params_struct = None
+        self._grads_struct = None
+        self._grad_flat = None
+        self._grad_views = None
 
     def _check_idx(self, t, name, shape_tail=None):
         if not torch.is_tensor(t) or t.dtype != torch.int64 or not t.is_cuda:

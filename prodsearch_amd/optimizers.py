@@ -222,6 +222,11 @@ class Optimizer(object):
         owner = self.zero_grads_owner() if self.zero_grads_owner is not None else None
         # only when the plan covers the model's whole flat gradient buffer (every view is the attached .grad)
         zero = owner is not None and all(p.grad is v for p, v in owner._grad_views)
+        if zero:             # ... and every such view is one this plan consumes (a word table made trainable after build_optim is not)
+            covered = plan.get('covered')
+            if covered is None:
+                covered = plan['covered'] = {id(p) for p in plan['live']}
+            zero = all(id(p) in covered for p, _ in owner._grad_views)
         hp.zero_grads = int(zero)
         _lib.check(lib.ps_clip_adam_dense(plan['dev'].data_ptr(), plan['n_chunks'], hp, plan['state'].data_ptr(),
                                           plan['gnorm'].data_ptr(), st), 'ps_clip_adam_dense')
