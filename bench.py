@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — train (u,q,i,neg) tuples/sec of the ranking-loss step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c4|c5] [--full]
 
 N > 1: either the driver's form (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ..., one rank
 per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or plain `python bench.py --gpus N`: with no
@@ -20,8 +20,9 @@ One step = trainer.py:74-78: loss = model(batch); model.zero_grad(); loss.backwa
 forward, backward, gradient exchange (N>1), clip+Adam.  Inputs are synthetic and already resident in HBM.
 
 Timing: `value` / `ms_per_step` = EXACTLY --steps steps between barrier + synchronize on both sides (max over ranks).
-Then, outside that region (rank 0 keeps the numbers): `median_ms_per_step` over --reps steps timed one by one with HIP
-events, and
+A plain run stops there: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full,
+outside that region (rank 0 keeps the numbers): at N > 1 the comm / compute split over a further --steps steps,
+`median_ms_per_step` over --reps steps timed one by one with HIP events, and
   roofline     — the workload's dominant kernel: algorithmic flops / bytes per launch ÷ its average IN-STEP duration,
                  measured live with one HIP event pair around every launch of it, on the stream it is launched on, over a
                  second pass of --steps steps (ps_ktimer_arm / ps_ktimer_read, include/prodsearch_hip.h)
@@ -29,7 +30,7 @@ events, and
                  gradients on the side stream (the fused forward of `roofline` is the longest on the critical path)
   cpu_baseline — the oracle (op-for-op CPU restatement; for c2 incl. the B*(K+1) replicated encoder) timed on this box's
                  host cores on a bounded sample: pools of 8, 32 and all hardware threads (rank 0, N=1)
-and, in the default c2 run at N=1 (bounded to about a minute; --no-also skips them):
+and, in the --full c2 run at N=1 (bounded to about a minute; --no-also skips them):
   roofline_hbm — the embedding-gather+score launch ALONE at the HBM-bound shape of configs[4] (d=256, 8 M-row item
                  table = 8.2 GB, B=1024 and B=8192; index sets rotate so that no row is re-read out of the 256 MB
                  Infinity Cache), event-timed per launch: the kernel the north star's 70 % target names
@@ -89,11 +90,14 @@ def parse(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--warmup', type=int, default=30)
-    ap.add_argument('--reps', type=int, default=200, help='steps timed one by one with HIP events for the median (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figure, also run every other leg: comm / compute split (N>1), median, roofline, '
+                         'cpu_baseline and, for c2 at N=1, roofline_hbm / also / fed_by_loader')
+    ap.add_argument('--reps', type=int, default=200, help='--full: steps timed one by one with HIP events for the median (0 = skip)')
     ap.add_argument('--dropout', type=float, default=0.1)
-    ap.add_argument('--cpu-steps', type=int, default=3, help='CPU-baseline steps per thread pool (0 = skip)')
-    ap.add_argument('--no-extras', action='store_true', help='skip median / roofline / cpu_baseline legs')
-    ap.add_argument('--no-also', action='store_true', help='default c2 run: skip the roofline_hbm / also legs')
+    ap.add_argument('--cpu-steps', type=int, default=3, help='--full: CPU-baseline steps per thread pool (0 = skip)')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip median / roofline / cpu_baseline legs')
+    ap.add_argument('--no-also', action='store_true', help='--full c2 run: skip the roofline_hbm / also legs')
     ap.add_argument('--workload', default='c2', choices=['c2', 'c4', 'c5'],
                     help='c2 = BASELINE configs[1] (the metric); c4 = configs[3] (RTM); c5 = per-GPU shard of configs[4]')
     ap.add_argument('--encoder', default='pvc', choices=['pvc', 'pv'], help='c4: review encoder')
@@ -479,7 +483,7 @@ def measure(a, name, rank, world, dev, steps, warmup, reps, extras, cpu_steps, i
     }
     if dumped is not None:
         out["dumped_outputs"] = {"dir": os.path.abspath(dump_dir), "files": len(dumped)}
-    if world > 1:
+    if world > 1 and a.full:
         # comm / compute split (every rank runs it; rank 0 keeps the numbers): a HIP event pair around every collective of the
         # step on the stream it is issued from (dist.comm_timing) and around each whole step, over a further `steps` steps
         pdist.comm_timing(True)
@@ -785,8 +789,8 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device('cuda', local)
     try:
-        out = measure(a, a.workload, rank, world, dev, a.steps, a.warmup, a.reps, not a.no_extras, a.cpu_steps, a.items,
-                      dump_dir=a.dump_outputs)
+        out = measure(a, a.workload, rank, world, dev, a.steps, a.warmup, a.reps, a.full and not a.no_extras, a.cpu_steps,
+                      a.items, dump_dir=a.dump_outputs)
     except Exception:
         if world > 1 and not (os.environ.get('PS_DP_RS') == 'rccl' and os.environ.get('PS_DP_AG') == 'rccl'):
             # (this process has initialised the GPU: nothing is retried here.  `python bench.py --gpus N` without torchrun does the
@@ -797,7 +801,7 @@ def main():
                              "only.\n" % (rank, world))
         raise
     later = out.pop("_cpu_baseline_later", None)
-    if a.workload == 'c2' and world == 1 and not a.no_extras and not a.no_also:
+    if a.workload == 'c2' and world == 1 and a.full and not a.no_extras and not a.no_also:
         out["roofline_hbm"] = gather_score_hbm_leg(dev)
         also = []
         for name, items in (('c5', ALSO_C5_ITEMS), ('c4', 0)):

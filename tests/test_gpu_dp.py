@@ -224,7 +224,7 @@ def test_review_transformer_two_ranks_of_32_equal_one_rank_of_64(tmp_path):
 
 def test_bench_contract_line_from_two_ranks_with_its_extra_legs():
     """The N>1 launch of bench.py exactly as the driver starts it (one process per rank, RANK / LOCAL_RANK / WORLD_SIZE /
-    MASTER_* from the environment; gloo here, both ranks on cuda:0), with the median / roofline legs on: they contain the
+    MASTER_* from the environment; gloo here, both ranks on cuda:0), with --full's median / roofline legs on: they contain the
     gradient exchange, so every rank has to run them — rank 0 alone would wait in its all-reduce for ever.  One JSON line,
     from rank 0 only, whole-job value = 2 ranks' tuples."""
     import json
@@ -234,7 +234,7 @@ def test_bench_contract_line_from_two_ranks_with_its_extra_legs():
     for r in range(2):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port),
                    HSA_ENABLE_IPC_MODE_LEGACY='0', PS_DIST_BACKEND='gloo', PS_BENCH_WATCHDOG='300')
-        procs.append(subprocess.Popen([sys.executable, bench, '--gpus', '2', '--steps', '6', '--warmup', '2', '--reps', '8'],
+        procs.append(subprocess.Popen([sys.executable, bench, '--gpus', '2', '--steps', '6', '--warmup', '2', '--full', '--reps', '8'],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -252,6 +252,7 @@ def test_bench_contract_line_from_two_ranks_with_its_extra_legs():
     assert d['n_gpus'] == 2 and d['steps'] == 6 and d['scaling'] == 'weak' and d['config']['parallelism'] == 'dp2'
     assert abs(d['value'] - 2 * 384 * 20 * 6 / (d['ms_per_step'] * 6e-3)) < 1e-6 * d['value']
     assert d['roofline']['launches_timed'] == 6 and 'median_ms_per_step' in d and 'cpu_baseline' not in d
+    assert 'comm_ms' in d and 'compute_ms' in d                          # --full at N > 1: the comm / compute split
 
 
 def test_bench_starts_its_own_ranks_when_no_launcher_did():
@@ -271,6 +272,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and d['config']['parallelism'] == 'dp2' and d['config']['global_batch'] == 768
     assert 'reduce-scatter' in d['config']['step']                     # the sharded optimizer is the dense default
+    assert not {'comm_ms', 'median_ms_per_step', 'roofline'} & set(d)    # a plain run (no --full) times its steps and nothing else
     if torch.cuda.device_count() < 2:
         env.pop('PS_DIST_BACKEND')
         p = subprocess.run([sys.executable, bench, '--gpus', '2', '--steps', '2', '--warmup', '0', '--no-extras'], env=env,

@@ -1,6 +1,6 @@
 # gpurun -- bash tools/ab_libs.sh [n]  : the C2 bench alternating between the diagnostic library (variant A) and the shipped one (B)
 n=${1:-3}
-B="python bench.py --steps 300 --warmup 30 --cpu-steps 0 --no-also"
+B="python bench.py --steps 300 --warmup 30 --full --cpu-steps 0 --no-also"
 for i in $(seq $n); do
   PS_DIAG_LIB=1 timeout -k 10 200 $B > gpurun_out/ab_a.txt 2>&1 || exit 1
   timeout -k 10 200 $B > gpurun_out/ab_b.txt 2>&1 || exit 1

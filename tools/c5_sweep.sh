@@ -8,5 +8,5 @@ for B in 1024 8192; do
 done
 done
 for cfg in "PS_SCORE_CH=0" "PS_SCORE_CH=2" "PS_SCORE_CH=4"; do
-  echo "C2 $cfg: $(env $cfg python bench.py --cpu-steps 0 --steps 200 2>/dev/null | python -c 'import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.4f ms/step, gather+score %.2f us %.0f GB/s" % (j["ms_per_step"], j["roofline"]["us_per_launch"], j["roofline"]["achieved"]))')"
+  echo "C2 $cfg: $(env $cfg python bench.py --full --cpu-steps 0 --steps 200 2>/dev/null | python -c 'import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.4f ms/step, gather+score %.2f us %.0f GB/s" % (j["ms_per_step"], j["roofline"]["us_per_launch"], j["roofline"]["achieved"]))')"
 done

@@ -1,7 +1,7 @@
 # gpurun -- bash tools/flat_xcd.sh : the flat weight-gradient group with / without the XCD-aware split placement (diagnostic library)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export PS_DIAG_LIB=1
-B="python bench.py --steps 300 --warmup 30 --cpu-steps 0 --no-also --reps 0"
+B="python bench.py --steps 300 --warmup 30 --full --cpu-steps 0 --no-also --reps 0"
 for rep in 1 2 3; do
 for e in "PS_FLAT_XCD=0" "PS_FLAT_XCD=1"; do
   env $e timeout -k 10 200 $B 2>/dev/null | python -c "

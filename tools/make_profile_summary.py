@@ -8,10 +8,10 @@ rows = list(csv.DictReader(open(stats)))
 pj = json.loads(open(prof_json).read().strip().splitlines()[-1])
 bj = json.loads(open(bench_json).read().strip().splitlines()[-1])
 out = []
-out.append("# Round %s — rocprofv3 --kernel-trace --stats of `python bench.py --steps %d --warmup %d --cpu-steps 0` (MI355X)\n"
+out.append("# Round %s — rocprofv3 --kernel-trace --stats of `python bench.py --steps %d --warmup %d --full --cpu-steps 0` (MI355X)\n"
            % (rnd[1:], pj['steps'], pj['warmup']))
 out.append("Command: `cd /tmp && export TMPDIR=/tmp; rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/final_prof "
-           "-- python3 bench.py --steps %d --warmup %d --cpu-steps 0`\n" % (pj['steps'], pj['warmup']))
+           "-- python3 bench.py --steps %d --warmup %d --full --cpu-steps 0`\n" % (pj['steps'], pj['warmup']))
 out.append("Workload: %s -> %d encoder replicas per row.\n" % (pj['config']['workload'], pj['config']['replicas_per_row']))
 out.append("| kernel | calls | avg µs | share |\n|---|---|---|---|")
 for r in rows:

@@ -23,7 +23,7 @@ Everything below is produced by `bash tools/refresh_profiles_r02.sh` on the GPU 
 and `python tools/make_profile_summary_r02.py`); the kernel statistics are `rocprofv3 --kernel-trace --stats --output-format csv --
 python3 bench.py ...` summaries.
 
-## C2 — `python bench.py` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
+## C2 — `python bench.py --full` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
 
 bench line (`r02_bench.json`): **%.0f tuples/s, %.4f ms/step**, median of 200 single steps %.4f ms (p10-p90 %.4f-%.4f), 13 kernel
 launches per step (+ the stream write / wait-value operations of the side stream; `r02_step_timeline.txt`: %s).
@@ -36,7 +36,7 @@ cycles `r02_sq_counters.txt`; why ~0.5 is the ceiling of that kernel: `r02_mlp_n
 
 Round 1 for comparison (`r01_bench.json`): 22.3 M tuples/s, 0.344 ms/step, 18 launches.
 
-## C4 — `python bench.py --workload c4` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
+## C4 — `python bench.py --workload c4 --full` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
 
 bench line (`r02_rtm_bench.json`): **%.0f tuples/s, %.4f ms/step** (median %.4f), 20 launches (round 1: 0.733 ms, 27 launches).
 Roofline object: `rtm_embed4_kernel`, bound `hbm`, %.0f GB/s of 8000 = **%.3f** on %.1f MB of algorithmic bytes (in-step %.1f µs):
@@ -46,7 +46,7 @@ the kernel is four dependent round trips per wave, not bytes (DESIGN.md 7c); PMC
 
 %s
 
-## C5 shard — `python bench.py --workload c5 --items 8000000` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
+## C5 shard — `python bench.py --workload c5 --items 8000000 --full` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
 
 bench line (`r02_c5_bench.json`): **%.0f tuples/s, %.3f ms/step**; roofline object: the stand-alone gather+score launch inside the step,
 %.0f GB/s = %.3f of peak (it shares the machine there); alone on the chip at this shape: `r02_gather_c5_shape.jsonl` (0.61 of 8 TB/s at

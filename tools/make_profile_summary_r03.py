@@ -28,7 +28,7 @@ Produced by `bash tools/refresh_profiles_r03.sh` on the GPU box, then `python to
 `python tools/make_profile_summary_r03.py`.  Kernel statistics are `rocprofv3 --kernel-trace --stats --output-format csv -- python3
 bench.py ...` summaries; counter passes (`--pmc`) ran alone, as the guide prescribes.
 
-## C2 — `python bench.py` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
+## C2 — `python bench.py --full` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
 
 bench line (`r03_bench.json`): **%.0f tuples/s, %.4f ms/step**, median of 200 single steps %.4f ms (p10-p90 %.4f-%.4f); round 2:
 27.8 M tuples/s, 0.276 ms; round 1: 22.3 M, 0.344 ms.  Timeline `r03_step_timeline.txt`: %s.
@@ -43,7 +43,7 @@ Kernel statistics (`r03_bench_kernel_stats.csv`, the timed steps plus the roofli
 
 %s
 
-## C4 — `python bench.py --workload c4` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
+## C4 — `python bench.py --workload c4 --full` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
 
 bench line (`r03_rtm_bench.json`): **%.0f tuples/s, %.4f ms/step** (median %.4f); round 2: 0.502 ms; round 1: 0.733 ms.
 Roofline object: `rtm_embed4_kernel`, bound `hbm`, %.0f GB/s of 8000 = **%.3f** on %.1f MB of algorithmic bytes (in-step %.1f µs; round
@@ -54,7 +54,7 @@ Cache (a 16.6 MB table), and the kernel's loads are no longer one round trip per
 
 %s
 
-## C5 shard — `python bench.py --workload c5 --items 8000000` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
+## C5 shard — `python bench.py --workload c5 --items 8000000 --full` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
 
 bench line (`r03_c5_bench.json`): **%.0f tuples/s, %.3f ms/step**; roofline object: the gather+score launch inside the step, %.0f GB/s =
 %.3f of peak (it shares the machine there; alone: `roofline_hbm` above and `r03_gather_c5_shape.jsonl`); PMC traffic

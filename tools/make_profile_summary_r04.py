@@ -42,7 +42,7 @@ Produced by `bash tools/refresh_profiles_r04.sh` on the GPU box, then `python to
 (+ `r04_gemm_x3d_diag.txt`, `r04_gemm_x3_bench.txt`, `r04_gemm_wgrad_ksplit.txt`); gather+score variants: `r04_gather_score_variants.jsonl`;
 alternative code paths: `r04_env_matrix.txt`.
 
-## C2 — `python bench.py` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
+## C2 — `python bench.py --full` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
 
 bench line (`r04_bench.json`): **%.0f tuples/s, %.4f ms/step**, median of 200 single steps %.4f ms (p10-p90 %.4f-%.4f), %d untimed
 pre-warm steps in front of the %d warm-up steps; round 3: 31.4-33.5 M tuples/s, 0.2305-0.245 ms; round 2: 27.8 M, 0.276; round 1: 22.3 M, 0.344.
@@ -60,7 +60,7 @@ Kernel statistics (`r04_bench_kernel_stats.csv`, the timed steps plus the roofli
 
 %s
 
-## C4 — `python bench.py --workload c4` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
+## C4 — `python bench.py --workload c4 --full` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
 
 bench line (`r04_rtm_bench.json`): **%.0f tuples/s, %.4f ms/step** (median %.4f); round 3: 0.388-0.398 ms; round 2: 0.502; round 1: 0.733.
 Roofline object: `rtm_embed4_kernel`, bound `hbm`, %.0f GB/s of 8000 = **%.3f** on %.1f MB of algorithmic bytes (in-step %.1f µs).
@@ -68,7 +68,7 @@ Timeline `r04_rtm_step_timeline.txt` (%s); kernel statistics (`r04_rtm_kernel_st
 
 %s
 
-## C5 shard — `python bench.py --workload c5 --items 8000000` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
+## C5 shard — `python bench.py --workload c5 --items 8000000 --full` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
 
 bench line (`r04_c5_bench.json`): **%.0f tuples/s, %.3f ms/step** (round 3: 1.34-1.39; the 50 M-row table in the default run's `also`:
 %.3f); roofline object: the gather+score launch inside the step, %.0f GB/s = %.3f of peak.  What moved it this round: the big weight

@@ -48,7 +48,7 @@ kernels: what their stores cost, why their chain is L2-bound, five experiments t
 `r05_score_bwd_wg_times.txt` (per-workgroup phases of the replica attention backward and of the score backward in the step),
 `r05_c4_wreduce_notes.md`, `r05_env_matrix.txt`.
 
-## C2 — `python bench.py` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
+## C2 — `python bench.py --full` (BASELINE configs[1]: item_transformer d=128, bs 384, 20 negatives, dropout 0.1)
 
 bench line (`r05_bench.json`): **%.0f tuples/s, %.4f ms/step**, median of 200 single steps %.4f ms (p10-p90 %.4f-%.4f), %d untimed
 pre-warm steps in front of the %d warm-up steps; round 4: 33.4-34.3 M tuples/s, 0.224-0.230 ms; round 3: 0.2305-0.245; round 2: 0.276; round 1: 0.344.
@@ -67,7 +67,7 @@ Kernel statistics (`r05_bench_kernel_stats.csv`, the timed steps plus the roofli
 
 %s
 
-## C4 — `python bench.py --workload c4` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
+## C4 — `python bench.py --workload c4 --full` (BASELINE configs[3]: review_transformer, bs 256, K 5, R 20+30, WL 100, pvc)
 
 bench line (`r05_rtm_bench.json`): **%.0f tuples/s, %.4f ms/step** (median %.4f); round 4: 0.382-0.387 ms; round 3: 0.388-0.398; round 2: 0.502; round 1: 0.733.
 Roofline object: `rtm_embed4_kernel` ALONE (the event pair is bound to its dispatch: round 4's scope also bracketed the 7 us group-list
@@ -76,7 +76,7 @@ Timeline `r05_rtm_step_timeline.txt` (%s); kernel statistics (`r05_rtm_kernel_st
 
 %s
 
-## C5 shard — `python bench.py --workload c5 --items 8000000` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
+## C5 shard — `python bench.py --workload c5 --items 8000000 --full` (one GPU's share of BASELINE configs[4]: d=256, bs 1024, row-sparse Adam)
 
 bench line (`r05_c5_bench.json`): **%.0f tuples/s, %.3f ms/step** (round 4: 1.25-1.30; the 50 M-row table in the default run's `also`:
 %.3f); roofline object: the gather+score launch inside the step (`score_fwd_sidx_kernel<4,16>`), %.0f GB/s = %.3f of peak (round 4: 0.41

@@ -3,9 +3,9 @@ set -e
 export PS_SIDE_EVENTS_NOTE="counter passes run with event-pair stream crossings (auto-detected from ROCPROF_COUNTER_COLLECTION)"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/refresh; rm -rf $O; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 100 --warmup 10 --cpu-steps 0 > $O/prof_bench.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 100 --warmup 10 --full --cpu-steps 0 > $O/prof_bench.json 2> $O/prof.err
 python tools/trace_step.py $O/prof > $O/step_timeline.txt
 echo "trace done"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 tools/gather_only.py > $O/pmc_fetch.log 2>&1

@@ -4,9 +4,9 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/refresh; rm -rf $O; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 100 --warmup 10 --cpu-steps 0 --no-also > $O/prof_bench.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 100 --warmup 10 --full --cpu-steps 0 --no-also > $O/prof_bench.json 2> $O/prof.err
 python tools/trace_step.py $O/prof > $O/step_timeline.txt
 cp $(ls -t $(find $O/prof -name '*kernel_stats.csv') | head -1) $O/bench_kernel_stats.csv
 echo "trace done"
@@ -18,7 +18,7 @@ rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INS
 python tools/pmc_summary.py $O/pmc_in | cut -c1-200 > $O/inst_counters.txt
 echo "mfma / sq counters done"
 # review transformer (configs[3])
-python bench.py --workload c4 --steps 200 --warmup 20 > $O/rtm_bench.json 2> $O/rtm_bench.err
+python bench.py --workload c4 --steps 200 --warmup 20 --full > $O/rtm_bench.json 2> $O/rtm_bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rtm_prof -- python3 bench.py --workload c4 --steps 60 --warmup 10 --cpu-steps 0 --no-extras > $O/rtm_prof.json 2> $O/rtm_prof.err
 cp $(ls -t $(find $O/rtm_prof -name '*kernel_stats.csv') | head -1) $O/rtm_kernel_stats.csv
 python tools/trace_step.py $O/rtm_prof 30 rtm_embed4 > $O/rtm_step_timeline.txt
@@ -33,7 +33,7 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_gw -- python3 tools/gat
 for B in 1024 8192; do python tools/gather_c5.py --rows 8000000 --batch $B --iters 50 2>/dev/null | tail -1; done > $O/gather_c5.log
 python tools/gather_only.py c2 2>/dev/null | tail -1 >> $O/gather_c5.log
 echo "gather done"
-python bench.py --workload c5 --items 8000000 --steps 100 --warmup 10 --cpu-steps 0 > $O/c5_bench.json 2> $O/c5_bench.err || true
+python bench.py --workload c5 --items 8000000 --steps 100 --warmup 10 --full --cpu-steps 0 > $O/c5_bench.json 2> $O/c5_bench.err || true
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5_prof -- python3 bench.py --workload c5 --items 8000000 --steps 30 --warmup 5 --cpu-steps 0 --no-extras > $O/c5_prof.json 2> $O/c5_prof.err
 python tools/trace_step.py $O/c5_prof > $O/c5_step_timeline.txt
 cp $(ls -t $(find $O/c5_prof -name '*kernel_stats.csv') | head -1) $O/c5_kernel_stats.csv
