@@ -137,6 +137,12 @@ const char* ps_arith_info(void);
  * this many replica rows upwards (default 1024, env PS_FUSE_BWD_MIN; below it five short launches are as fast).  The
  * parity tests set it to 1 to drive the fused kernel through the small golden cases.  Returns the previous value. */
 int ps_set_fuse_bwd_min(int rows);
+/* Tuning knob (no reference counterpart): with replicas and the fused per-replica backward, that kernel adds the item rows'
+ * gradients (product_emb / product_bias) itself and the score backward's launch is its word tasks only (default 1, env
+ * PS_ITEM_SCATTER_FUSED; 0 = the score backward's own item workgroups).  Deterministic mode never takes the form.  Returns
+ * the previous value.  ps_item_scatter_fused_taken: 1 when the last backward of this process took it. */
+int ps_set_item_scatter_fused(int on);
+int ps_item_scatter_fused_taken(void);
 /* Tuning knob: how the backward's side stream crosses the main stream.  Bit 1: a join is a stream write-value / wait-value
  * pair instead of an event pair; bit 0: a fork is a wait-value on the side stream whose value the NEXT kernel launched on the
  * main stream stores as its first workgroup starts (every earlier main-stream kernel has completed by then) — the main stream

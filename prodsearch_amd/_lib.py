@@ -110,6 +110,8 @@ SYMBOLS = {
     'ps_last_error': (C.c_char_p, []),
     'ps_arith_info': (C.c_char_p, []),
     'ps_set_fuse_bwd_min': (C.c_int, [C.c_int]),
+    'ps_set_item_scatter_fused': (C.c_int, [C.c_int]),
+    'ps_item_scatter_fused_taken': (C.c_int, []),
     'ps_set_side_mode': (C.c_int, [C.c_int]),
     'ps_side_values_in_use': (C.c_int, []),
     'ps_set_deterministic': (C.c_int, [C.c_int]),

@@ -498,7 +498,17 @@ int launch_mlp_fwd_fused(const MlpFwdArgs& a, hipStream_t st) {
 //   d ctx^T = Wo^T . dout^T  (4 output blocks x 2 reduction halves over the 8 waves, halves met in LDS)
 // Writes only what the weight gradients and the fan-in residual read (do2, da1, dy1, dout, dctx) and parks the seven
 // bias / gamma / beta column sums per workgroup (fixed-order sums: bitwise reproducible).
-template <int NBW, int PF>
+// ISC (item transformer with replicas, MlpBwdArgs::g_product_emb): the kernel also scatters the item rows' gradients — the
+// prologue holds ds(m) and idx(m) of every replica row for d enc, so  g_product_emb[idx(m)] += ds(m) * enc[m]  needs only the
+// stored enc row: the 504 item workgroups of the score backward (C2), which re-derived both, are not launched.  A wave owns the
+// 4 rows of its LayerNorm stages; per row two coalesced 256-byte loads (requested at the top of the prologue) and two 256-byte
+// no-return atomics.  The atomics are SPREAD over the chain, one row in front of each of its product loops: the 1 M adds of a
+// launch take the L2s' atomic units ~6 us, and issued together — by every workgroup at once — they are a tail of that length
+// (behind the last barrier: 27.7 -> 33.6 us; in the prologue 32.2; behind the chain 29.6), while a row at a time between the
+// chain's weight requests they cost nothing measurable (28.1-28.9 us: profiles/item_scatter_fused_notes.md).  Every load and
+// atomic is unconditional: a row past M or the padding item adds 0.f to a real address (the padding row's gradient stays
+// exactly zero).
+template <int NBW, int PF, bool ISC>
 __global__ __launch_bounds__(MT_THREADS, 2) void mlp_bwd_t_kernel(const MlpBwdArgs a) {
   fork_signal(a.sig, a.sigval);
   extern __shared__ float lds_raw[];
@@ -522,6 +532,21 @@ __global__ __launch_bounds__(MT_THREADS, 2) void mlp_bwd_t_kernel(const MlpBwdAr
     const int which = tid >> 5, q = tid & 31;
     *reinterpret_cast<float4*>(&L.vec[which][4 * q]) = *reinterpret_cast<const float4*>((which == 0 ? a.gf : a.g1) + 4 * q);
   }
+  float isc_e[4][2], isc_ds[4]; int isc_idx[4]; bool isc_live[4];
+  if (ISC) {   // the wave's 4 enc rows (lane = column, two halves): two coalesced 256-byte loads per row
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int mr = m0 + 4 * wave + r;
+      const float* er = a.enc + (size_t)(mr < M ? mr : 0) * MD + lane;
+      isc_e[r][0] = er[0]; isc_e[r][1] = er[64];
+    }
+  }
+  auto isc_add = [&](const int r) {
+    float* g = a.g_product_emb + (size_t)isc_idx[r] * MD + lane;
+    atomicAdd(g, isc_live[r] ? isc_ds[r] * isc_e[r][0] : 0.f);
+    atomicAdd(g + 64, isc_live[r] ? isc_ds[r] * isc_e[r][1] : 0.f);
+    if (a.g_product_bias && lane == 0) atomicAdd(&a.g_product_bias[isc_idx[r]], isc_ds[r]);
+  };
   // LayerNorm inputs of this lane's elements: y2 (final LN) now, y1 (FF LN) too — both are needed across the main phase
   float x2[8], st2[2] = {0.f, 0.f};
   {
@@ -549,6 +574,14 @@ __global__ __launch_bounds__(MT_THREADS, 2) void mlp_bwd_t_kernel(const MlpBwdAr
     const float4 v0 = *reinterpret_cast<const float4*>(row), v1 = *reinterpret_cast<const float4*>(row + 4);
     dy[0] = ds * v0.x; dy[1] = ds * v0.y; dy[2] = ds * v0.z; dy[3] = ds * v0.w;
     dy[4] = ds * v1.x; dy[5] = ds * v1.y; dy[6] = ds * v1.z; dy[7] = ds * v1.w;
+    if (ISC) {   // ds / idx of the wave's row r from lane 16 r: wave-uniform per row
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        isc_ds[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ds), 16 * r));
+        isc_idx[r] = __builtin_amdgcn_readlane((int)idx, 16 * r);
+        isc_live[r] = m0 + 4 * wave + r < M && isc_idx[r] != (int)a.P;   // (a row past M: ds = 0, idx and enc row of row 0)
+      }
+    }
   } else {
     const float* src = a.denc + (size_t)(ok ? mg : 0) * MD + c8;
     const float4 v0 = ok ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -654,6 +687,10 @@ __global__ __launch_bounds__(MT_THREADS, 2) void mlp_bwd_t_kernel(const MlpBwdAr
     for (int r = 0; r < 16; ++r) acc1[r] = 0.f;
     uint4 bq[2][3];                                                    // the B operand of step t + 1 is read under step t's MFMAs
     read_b(bq[0], L.Xa, l31, 8 * h);
+    if (ISC) {   // (the wave's 4 rows over the chain's 2 NBW product loops)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) if (r * NBW / 2 == 2 * bi) isc_add(r);
+    }
     { if ((wave >= 4) == (bi == 0)) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
 #pragma unroll
     for (int t = 0; t < 8; ++t) {                                      // d h1^T block = W2^T[block rows] . do2^T
@@ -703,6 +740,10 @@ __global__ __launch_bounds__(MT_THREADS, 2) void mlp_bwd_t_kernel(const MlpBwdAr
       const float hi8[8] = {dv[8], dv[9], dv[10], dv[11], dv[12], dv[13], dv[14], dv[15]};
       split8(lo8, df[0]);
       split8(hi8, df[1]);
+    }
+    if (ISC) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) if (r * NBW / 2 == 2 * bi + 1) isc_add(r);
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {                                      // d ln1^T += W1^T[:, block] . d a1^T block
@@ -785,19 +826,33 @@ int launch_mlp_bwd_fused(const MlpBwdArgs& a, hipStream_t st) {
   PS_REQUIRE(mlp_x3_enabled(a.F) && a.M > 0, "fused mlp backward: F=%d M=%d (F must be 256, 512 or 1024)", a.F, a.M);
   PS_REQUIRE(a.part_f && a.part_1 && a.part_b1, "fused mlp backward: column sums must be parked");
   PS_REQUIRE(a.x3.on && a.x3.bwd_wo && a.x3.bwd_ff, "fused mlp backward: the weight fragment streams are missing (WSplit)");
+  const bool isc = a.g_product_emb != nullptr;
+  PS_REQUIRE(!isc || (a.item_scores && a.enc && a.M == a.B * (a.K + 1)), "fused mlp backward: the item scatter needs the scores, enc and M = B (K + 1)");
   KTimeScope kt("mlp_bwd", st);
   MlpBwdArgs b = a;
   b.sig = nullptr; b.sigval = 0;
   b.stamp = g_mlp_stamp ? g_mlp_stamp + 128 : nullptr;
   const dim3 grid(ps_cdiv(a.M, MBM)), block(MT_THREADS);
-  static bool a1 = false, a2 = false, a4 = false;
-  if (a.F == 256) TRY(set_lds_attr(mlp_bwd_t_kernel<1, 3>, a1));
-  else if (a.F == 512) TRY(set_lds_attr(mlp_bwd_t_kernel<2, 3>, a2));
-  else TRY(set_lds_attr(mlp_bwd_t_kernel<4, 3>, a4));
+  static bool a1 = false, a2 = false, a4 = false, s1 = false, s2 = false, s4 = false;
+  if (isc) {
+    if (a.F == 256) TRY(set_lds_attr(mlp_bwd_t_kernel<1, 3, true>, s1));
+    else if (a.F == 512) TRY(set_lds_attr(mlp_bwd_t_kernel<2, 3, true>, s2));
+    else TRY(set_lds_attr(mlp_bwd_t_kernel<4, 3, true>, s4));
+  } else {
+    if (a.F == 256) TRY(set_lds_attr(mlp_bwd_t_kernel<1, 3, false>, a1));
+    else if (a.F == 512) TRY(set_lds_attr(mlp_bwd_t_kernel<2, 3, false>, a2));
+    else TRY(set_lds_attr(mlp_bwd_t_kernel<4, 3, false>, a4));
+  }
   side_take_signal(st, &b.sig, &b.sigval);             // (every check is behind us: the launch happens)
-  if (a.F == 256) hipLaunchKernelGGL((mlp_bwd_t_kernel<1, 3>), grid, block, sizeof(MlpTLds), st, b);
-  else if (a.F == 512) hipLaunchKernelGGL((mlp_bwd_t_kernel<2, 3>), grid, block, sizeof(MlpTLds), st, b);
-  else hipLaunchKernelGGL((mlp_bwd_t_kernel<4, 3>), grid, block, sizeof(MlpTLds), st, b);
+  if (isc) {
+    if (a.F == 256) hipLaunchKernelGGL((mlp_bwd_t_kernel<1, 3, true>), grid, block, sizeof(MlpTLds), st, b);
+    else if (a.F == 512) hipLaunchKernelGGL((mlp_bwd_t_kernel<2, 3, true>), grid, block, sizeof(MlpTLds), st, b);
+    else hipLaunchKernelGGL((mlp_bwd_t_kernel<4, 3, true>), grid, block, sizeof(MlpTLds), st, b);
+  } else {
+    if (a.F == 256) hipLaunchKernelGGL((mlp_bwd_t_kernel<1, 3, false>), grid, block, sizeof(MlpTLds), st, b);
+    else if (a.F == 512) hipLaunchKernelGGL((mlp_bwd_t_kernel<2, 3, false>), grid, block, sizeof(MlpTLds), st, b);
+    else hipLaunchKernelGGL((mlp_bwd_t_kernel<4, 3, false>), grid, block, sizeof(MlpTLds), st, b);
+  }
   PS_LAUNCH_CHECK();
   return PS_OK;
 }

@@ -25,6 +25,8 @@ struct ScoreArgs {
   const float* scale_dev;        // optional device scalar multiplied into scale
   float* denc;                   // [B*R,d]  (null: the consumer derives d enc from the scores itself, MlpBwdArgs::item_scores)
   int part;                      // replicas only: 0 = everything, 1 = d enc only (no table scatter), 2 = table scatter only
+  int items_elsewhere;           // replicas, part 0, denc null: the fused per-replica backward adds the item rows' gradients itself
+                                 // (MlpBwdArgs::g_product_emb) — the launch is the 2*B word-task workgroups, no item workgroups
   float* g_product_emb; float* g_word_emb; float* g_product_bias; float* g_word_bias;
   // ---- folded form (TEM with replicas, the wave-specialised fused MLP forward): no gather+score / loss launches.
   //  * the word tasks (item_to_words, item_transformer.py:260-283: encoder-independent) run as extra workgroups of the
@@ -356,6 +358,9 @@ struct MlpBwdArgs {
   // optional: d enc computed from the scores instead (TEM with replicas: row m = (b, j), M = B*(K+1))
   const float* item_scores; const int64_t* target; const int64_t* neg_items; const float* product_emb;
   int B, K, pos_weight; int64_t P; float scale; const float* scale_dev;
+  // optional, with item_scores: the kernel also scatters the item rows' gradients, g_product_emb[idx(m)] += ds(m) * enc[m]
+  // (the item tasks of score_bwd_kernel, which then runs with ScoreArgs::items_elsewhere), from the ds / idx it holds anyway
+  const float* enc; float* g_product_emb; float* g_product_bias;   // enc: the forward's stored rows [M,128]; bias: null unless bias_product
   const float* y2; const float* stf; const float* gf;  // final LN: input, {mean, rstd}, gamma
   const float* y1; const float* st1; const float* g1;  // FF LN
   const float* a1;                                     // [M,F] pre-activation of the hidden layer

@@ -1613,6 +1613,7 @@ __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void score_bwd_det_kernel(c
 int launch_score_bwd(const ScoreArgs& a, hipStream_t st) {
   PS_REQUIRE(a.d % 32 == 0 && a.d <= 32 * BW_MAXE, "score bwd: d=%d unsupported", a.d);
   if (ps_deterministic()) {
+    PS_REQUIRE(!a.items_elsewhere, "score bwd: the deterministic scatter owns the item rows too");
     // d enc (part 1: no table scatter) keeps its kernel — its sums are per row, in a fixed order; the table scatter
     // (part 2) goes through the sole-owner form
     if (a.denc && a.part != 2) {
@@ -1642,7 +1643,9 @@ int launch_score_bwd(const ScoreArgs& a, hipStream_t st) {
     }
     return PS_OK;
   }
-  const int item_wgs = a.R > 1 ? ps_cdiv(a.B * (a.K + 1), SB_RG) : 0;
+  PS_REQUIRE(!a.items_elsewhere || (a.R > 1 && a.part == 0 && !a.denc), "score bwd: items_elsewhere needs replicas, part 0 and no d enc");
+  // items_elsewhere: the 2*B word-task workgroups only (the kernel's item_wg test is then false for every workgroup)
+  const int item_wgs = a.R > 1 && !a.items_elsewhere ? ps_cdiv(a.B * (a.K + 1), SB_RG) : 0;
 #if PS_DIAG_ON
   ScoreArgs as = a;
   as.stamp = ps_diag_int("PS_SBW_STAMP", 0) ? ps_debug_stamp_ptr() : nullptr;

@@ -1138,12 +1138,31 @@ extern "C" int ps_set_fuse_bwd_min(int rows) {
   return old;
 }
 
+// The item rows' gradient scatter (g_product_emb[idx(b, j)] += ds * enc[(b, j)]) rides in the fused per-replica backward, which
+// holds ds and idx already, and the score backward's launch shrinks to its word tasks (MlpBwdArgs::g_product_emb,
+// ScoreArgs::items_elsewhere), which then are the main stream's last launch instead of the side stream's first (see
+// enc_layers_backward).  PS_ITEM_SCATTER_FUSED=0: the score backward's own item workgroups, on the side stream, as before.
+// Deterministic mode never takes it (its sole-owner scatter walks the item tasks in order).
+static int& item_scatter_fused_slot() {
+  static int v = ps_env_int("PS_ITEM_SCATTER_FUSED", 1);
+  return v;
+}
+extern "C" int ps_set_item_scatter_fused(int on) {
+  const int old = item_scatter_fused_slot();
+  item_scatter_fused_slot() = on;
+  return old;
+}
+static int g_item_scatter_taken = 0;     // the last backward's fused kernel scattered the item rows
+extern "C" int ps_item_scatter_fused_taken(void) { return g_item_scatter_taken; }
+
 // K/V/Q weight gradients of the first layer that the caller launches on the main stream AFTER its embedding scatter
 // (PS_WG3_LAST, item transformer): the scatter (atomics) then shares the machine with the side stream's W2 / W1 / Wo
 // products, and these follow when those are nearly through, instead of slowing each other down product beside product
 static thread_local GemmProblem g_wg3_last[4];
 static thread_local int g_wg3_last_n = 0;
 static thread_local bool g_wg3_defer_ok = false;          // set by a caller that will flush them
+// ... and, when the fused backward has scattered the item rows, the score backward's word tasks behind them (see there)
+static thread_local bool g_score_words_last = false;
 static int flush_wg3_last(hipStream_t st) {
   const int n = g_wg3_last_n;
   g_wg3_last_n = 0;
@@ -1165,6 +1184,7 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
   side_set_light((int64_t)B * S * d <= ((int64_t)2 << 20));   // C2: 1.03 M elements of x; review transformer 10 M; C5 5.5 M
   static const bool bwd_fuse_on = ps_env_int("PS_NO_FUSE_BWD", 0) == 0;
   const int bwd_fuse_min = fuse_bwd_min_slot();
+  g_item_scatter_taken = 0;
   const bool fuse_last = NL > 0 && fold && bwd_fuse_on && ps_fusion_enabled() && w.layer[NL - 1].Sq == 1 &&
                          mlp_fused_serves(d, F) && w.wsplit && w.layer[NL - 1].M2 == w.Mf && w.Mf >= bwd_fuse_min &&
                          mlp_bwd_fused_blocks(w.Mf) <= w.lnrows && fold->n + 3 <= PS_MAX_COLFOLD;
@@ -1227,6 +1247,10 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
         const ScoreArgs& sa = *score_on_side;
         m.item_scores = sa.item_scores; m.target = sa.target; m.neg_items = sa.neg_items; m.product_emb = sa.product_emb;
         m.B = sa.B; m.K = sa.K; m.pos_weight = sa.pos_weight; m.P = sa.P; m.scale = sa.scale; m.scale_dev = sa.scale_dev;
+        if (item_scatter_fused_slot() != 0 && !ps_deterministic() && g_wg3_defer_ok && sa.part == 0 && sa.enc && sa.g_product_emb) {
+          m.enc = sa.enc; m.g_product_emb = sa.g_product_emb;
+          m.g_product_bias = sa.bias_product ? sa.g_product_bias : nullptr;
+        }
       }
       m.x3 = make_wsplit(D, P, ws, w);                 // the fragment streams the forward's embed launch left in the workspace
       m.do2 = const_cast<float*>(do2); m.da1 = ws + w.da1; m.dy1 = ws + w.dy1;
@@ -1257,7 +1281,16 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
       GemmProblem wg1[1] = {gp_wgrad(ws + w.da1, F, ws + l.ln1, d, Lg.w1, F, d, M2)};
       GemmProblem wgo[1] = {gp_wgrad(m.dout, d, ws + l.ctx, d, Lg.wo, d, d, M2)};
       TRY(side_fork(st));                           // fork 1: W2, W1, Wo weight gradients under the attention backward
-      if (score_on_side) {                          // ... led by the table scatter of the score backward (behind them instead: 0.284 -> 0.293 ms/step)
+      if (score_on_side && m.g_product_emb) {
+        // the fused kernel above has added the item rows: what is left of the score backward are its word tasks (2 B workgroups,
+        // 14 us alone at C2).  Leading the side stream, as the whole scatter does below, they only moved the W2 / W1 / Wo group
+        // into the attention backward and the embedding scatter (42 -> 52-58 us, the side stream still the last to end: a wash);
+        // the caller launches them as the main stream's LAST kernel instead, behind its K / V / Q weight gradients — the main
+        // stream ended 12 us before the side stream, which now carries the group alone, and the join's value is there when the
+        // main stream arrives (C2 0.2133 -> 0.2067 ms/step, profiles/item_scatter_fused_notes.md)
+        g_score_words_last = true;
+        g_item_scatter_taken = 1;
+      } else if (score_on_side) {                   // ... led by the table scatter of the score backward (behind them instead: 0.284 -> 0.293 ms/step)
         ScoreArgs t = *score_on_side;
         t.denc = nullptr;
         SideCtx* sc = side_ctx_on(st);
@@ -1486,6 +1519,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
                              float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
                              ps_stream_t stream) {
   enc_clear_call_flags();
+  g_item_scatter_taken = 0;
   PS_REQUIRE(desc && params && batch && ws && grads, "backward: null argument");
   PsTemDesc D = *desc;
   D.C = 0;
@@ -1521,13 +1555,16 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the dX products read the TRANSPOSED weight planes (gemm.hip)
   ColFoldList fold;
   fold.n = 0;
+  bool score_words_last = false;    // enc_layers_backward left the score backward's word tasks to this function (its last launch)
   const float* dqe = ws + w.denc;   // grad wrt query_emb rows (QEM: enc IS query_emb)
   int lddqe = d;
   if (tem) {
-    g_wg3_defer_ok = true; g_wg3_last_n = 0;
+    g_wg3_defer_ok = true; g_wg3_last_n = 0; g_score_words_last = false;
     const int rc_enc = enc_layers_backward(D, P, G, batch->u_item_idxs, nullptr, ws, w, st, &fold, score_deferred ? &s : nullptr,
                                            rows_list_ok(D));
     g_wg3_defer_ok = false;
+    score_words_last = g_score_words_last;
+    g_score_words_last = false;
     if (rc_enc != PS_OK) { g_wg3_last_n = 0; return rc_enc; }
     dqe = ws + w.dx;      // row 0 of each sequence is the query embedding
     lddqe = S * d;
@@ -1582,6 +1619,11 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
     g_wg3_last[g_wg3_last_n++] = gp_wgrad(ws + w.dqpre, d, ws + w.qmean, d, G.fs_w, d, d, B);
   }
   TRY(flush_wg3_last(st));
+  if (score_words_last) {      // the word tasks of the score backward (the fused backward has scattered the item rows)
+    ScoreArgs t = s;
+    t.denc = nullptr; t.items_elsewhere = 1;
+    TRY(launch_score_bwd(t, st));
+  }
   TRY(side_join(st));
   return PS_OK;
 }
