@@ -81,7 +81,10 @@ __device__ inline void adam_step_scalars(const PsAdamHyper& hp, int64_t step, fl
 __device__ inline void adam_scalars(const PsAdamHyper& hp, float total_sumsq, int64_t step, float* out, float* norm_out) {
   const float norm = sqrtf(total_sumsq);
   float coef = 1.f;
-  if (hp.max_grad_norm > 0.f) coef = fminf(hp.max_grad_norm / (norm + 1e-6f), 1.f);
+  if (hp.max_grad_norm > 0.f) {
+    const float c = hp.max_grad_norm / (norm + 1e-6f);
+    coef = c >= 1.f ? 1.f : c;         // (not fminf: a NaN norm must give a NaN coefficient, as clip_grad_norm_'s clamp does)
+  }
   out[0] = coef * hp.grad_scale;
   adam_step_scalars(hp, step, &out[1], &out[2], &out[3]);
   *norm_out = norm;

@@ -22,7 +22,7 @@ def _ref_optimizer(method, params, lr, wd, accum):
         return o
     if method == 'adadelta':
         return torch.optim.Adadelta(params, lr=lr, weight_decay=wd)
-    raise ValueError(method)         # (Adam: tests/test_gpu_parity.py against the reference's own fixtures)
+    raise ValueError(method)         # (Adam: tests/test_gpu_adam_direct.py, element by element against a float64 Adam)
 
 
 @pytest.mark.parametrize('method', ['sgd', 'adagrad', 'adadelta'])
