@@ -35,29 +35,70 @@ int make_ws(const PsTemDesc& D, Ws& w);
 // the last layer's weights as the fused kernels' bf16x3 planes inside the workspace (on = 0 when the x3 form is not taken)
 WSplit make_wsplit(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w);
 
+// ------------------------------------------------------------- one plan per call
+// Which path every step of the encoder takes, decided once per call by enc_plan (host only, no launches) from the shapes, the
+// weights present and the switches; the forward, the backward and their callers read it instead of deciding again.
+enum AttnForm {
+  ATTN_GENERIC,             // any Sq (launch_attn_fwd / launch_attn_bwd)
+  ATTN_SQ1,                 // one query row: a workgroup per sequence, replicas share K / V in LDS
+  ATTN_W1,                  // ... no replicas: a wave per sequence
+  ATTN_WF,                  // ... replicas: a wave per (sequence, four heads)
+  ATTN_KVQ                  // layer 0 of a one-layer encoder: K / V / Q projections + the wf attention in one forward launch
+};
+struct EncPlan {
+  AttnForm attn[PS_MAX_LAYERS];
+  bool rowlist;             // the (one-layer) encoder walks the valid-row list: padded rows of x are read nowhere, need not be written
+  bool fwd_fuse_last;       // last layer's Wo + LN + FFN + final LN as one forward kernel (mlp_fused.hip)
+  bool fold_score;          // ... whose epilogue can take item scoring + loss (ScoreArgs, folded form)
+  struct Bwd {
+    bool fuse_last;         // the last layer's whole per-replica backward as one kernel; needs the caller's ColFoldList
+    bool item_scatter;      // ... which may scatter the item rows' gradients too (ps_set_item_scatter_fused; never deterministic)
+    bool wg3_main;          // ... and whose K / V / Q weight gradients follow the dX product on the main stream
+    bool wg3_last;          // ... as the caller's last launches, where it flushes them (EncBwdIn::caller_flushes_tail)
+    bool wgrad_early;       // unfused form: W2 / W1 weight gradients fork as soon as d a1 exists
+    bool q_folded;          // layer 0: dQ.Wq rides in the attention backward's tail
+    bool listed;            // one layer: dK / dV, their weight gradients and the dX product walk the valid-row list
+    bool presum;            // ... with the replicas' fan-in summed by a launch of its own (dQ.Wq not folded)
+    bool dx_fused;          // ... or no dX product at all: the attention backward leaves d x as two partial rows
+  } bwd;
+};
+// `rows_listed`: w.vrows / w.vcount hold the list of valid (non-pad) rows of x (EmbedArgs::vrows, or the review transformer's
+// rtm_rowlist_kernel).  `valid`: the key-padding mask the layer loops will get (below); null for u_item_idxs.
+EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed, const float* valid);
+
 // All encoder layers + the final LayerNorm on the consumed position: reads w.x, writes w.enc.
 // Key-padding mask: `valid` [n_seq, S] floats if given, else u_item_idxs != P (TEM).
-// `rows_listed`: w.vrows / w.vcount hold the list of valid (non-pad) rows of x (EmbedArgs::vrows, or the review
-// transformer's rtm_rowlist_kernel); the K/V products of a one-layer encoder then run over those rows only.
-// `fold_sc` (optional, TEM with replicas): item scoring + loss run in the epilogue of the last layer's fused kernel.
+struct EncFwdOpts {
+  bool rows_listed = false;            // as for enc_plan; the K/V products of a one-layer encoder then run over those rows only
+  const ScoreArgs* fold_sc = nullptr;  // TEM with replicas: item scoring + loss run in the epilogue of the last layer's fused kernel
+  bool split_bwd_left = false;         // the embed launch left the backward-only weight streams to the fused projection + attention launch
+};
 int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
-                       const Ws& w, hipStream_t st, bool rows_listed = false, const ScoreArgs* fold_sc = nullptr);
-bool enc_rowlist_taken(const PsTemDesc& D, const Ws& w, bool rows_listed);   // the encoder reads x through the valid-row list only
+                       const Ws& w, hipStream_t st, const EncFwdOpts& o);
 // Backward of the above: reads w.denc (grad wrt w.enc), accumulates parameter grads into G, writes w.dx.
-// `fold` (optional): the LayerNorm backwards park their column sums in w.lnpart and append to this list; the caller
-// must hand it to a later launch_embed_scatter (EmbedBwdArgs::fold).  nullptr: plain atomics.
-// `score_on_side` (optional, TEM with replicas): the caller has NOT launched the score backward; when the last layer's
-// backward is fused, d enc is derived from the scores inside that kernel and the score backward (table scatter only) is
-// launched on the side stream behind it, off the dependent chain; otherwise it is launched first, as usual.
+struct EncBwdIn {
+  // the LayerNorm backwards park their column sums in w.lnpart and append to this list; the caller must hand it to a later
+  // launch_embed_scatter (EmbedBwdArgs::fold).  nullptr: plain atomics
+  ColFoldList* fold = nullptr;
+  // TEM with replicas: the caller has NOT launched the score backward; when the last layer's backward is fused, d enc is derived
+  // from the scores inside that kernel and the score backward (table scatter only) is launched on the side stream behind it, off
+  // the dependent chain; otherwise it is launched first, as usual
+  const ScoreArgs* score_on_side = nullptr;
+  bool rows_listed = false;
+  bool caller_flushes_tail = false;    // the caller launches EncBwdOut's deferred work behind its embedding scatter
+};
+struct EncBwdOut {
+  bool dx_two_partials = false;        // the attention backward left d x as two partial rows per position (dx and dxn, AttnArgs::dxp)
+  // K/V/Q weight gradients of the first layer that the caller launches on the main stream AFTER its embedding scatter
+  // (PS_WG3_LAST, item transformer): the scatter (atomics) then shares the machine with the side stream's W2 / W1 / Wo
+  // products, and these follow when those are nearly through, instead of slowing each other down product beside product
+  GemmProblem wg3_last[4]; int wg3_last_n = 0;   // (the fourth slot: the caller's own f_W weight gradient)
+  bool score_words_last = false;       // ... and, when the fused backward has scattered the item rows, the score backward's word tasks behind them
+  bool item_scatter_taken = false;     // the fused kernel scattered the item rows
+};
+void enc_record_backward(const EncBwdOut& out);   // once per backward entry point: what ps_item_scatter_fused_taken() reports
 int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui,
-                        const float* valid, float* ws, const Ws& w, hipStream_t st, ColFoldList* fold = nullptr,
-                        const ScoreArgs* score_on_side = nullptr, bool rows_listed = false);
-
-// What enc_layers_forward / enc_layers_backward hand to their caller's next step (thread-local, tem.hip): every entry point
-// clears them on entry and on its error returns.  enc_take_dx_two_partials: the attention backward left d x as two partial
-// rows per position (dx and dxn, AttnArgs::dxp) — read once, cleared by the read.
-void enc_clear_call_flags();
-bool enc_take_dx_two_partials();
+                        const float* valid, float* ws, const Ws& w, hipStream_t st, const EncBwdIn& in, EncBwdOut& out);
 
 // ZAM / AEM (attn_emb.hip): the attention-embedding step between the query encoder and the scoring.  ae_forward reads
 // w.query_emb and writes w.enc [B*R,d]; ae_backward reads w.denc and leaves d query_emb in w.ae_dqe [B,d].

@@ -1901,11 +1901,11 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
   PS_REQUIRE(!e.fs || (P.fs_w && P.fs_b), "rtm: null FS encoder weights");
   const bool fs_fused = e.fs && ps_fusion_enabled() && d <= 128;
   if (fs_fused) { e.fs_w = P.fs_w; e.fs_b = P.fs_b; }
-  {
-    PsTemTensors Ts;
-    to_tem_tensors(P, Ts);
-    e.split = make_wsplit(E, Ts, ws + r.enc_base, w);      // the fused kernels' bf16x3 weight planes ride in this launch
-  }
+  const bool listed = rtm_rows_listed(r, w);
+  PsTemTensors T;
+  to_tem_tensors(P, T);
+  const EncPlan plan = enc_plan(E, T, ws + r.enc_base, w, listed, ws + r.valid);   // what enc_layers_forward will decide
+  e.split = make_wsplit(E, T, ws + r.enc_base, w);      // the fused kernels' bf16x3 weight planes ride in this launch
   // the backward's inverted index (rtm_counts_in_forward): its counters are cleared by this launch, filled by the next
   const bool use_e4 = rtm_embed4_taken(D, k, r);
   k.count_fwd = rtm_counts_in_forward(D, k, r);
@@ -1927,7 +1927,7 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
       // x rows of padded positions: with the valid-row list nothing downstream reads them (the projections, the attention and
       // the backward all walk the list), so they are not written either (18 us of the launch at C4, 73 % padding)
       static const bool keep_pads = ps_diag_int("PS_RTM_WRITE_PADS", 0) != 0;
-      const int pads_unread = enc_rowlist_taken(E, w, rtm_rows_listed(r, w)) && !k.raw && !keep_pads ? 1 : 0;
+      const int pads_unread = plan.rowlist && !k.raw && !keep_pads ? 1 : 0;
       const FDiv fR = make_fdiv(D.R), fK = make_fdiv(D.K > 0 ? D.K : 1);
       // the valid-group list (rtm_grouplist_kernel): only when padded rows of x are not read and the counter is cleared by
       // the query-encoder launch (training).  PS_RTM_GROUPLIST=0: every group gets a wave, as in round 2.
@@ -1960,15 +1960,13 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
     hipLaunchKernelGGL(rtm_fs_finish_kernel, dim3(ps_cdiv(nslots, 4)), dim3(256), 0, st, k);
     PS_LAUNCH_CHECK();
   }
-  const bool listed = rtm_rows_listed(r, w);
   if (listed) {
     hipLaunchKernelGGL(rtm_rowlist_kernel, dim3(ps_cdiv(r.Bseq, 4)), dim3(256), 0, st, k);
     PS_LAUNCH_CHECK();
   }
-  PsTemTensors T;
-  to_tem_tensors(P, T);
-  TRY(enc_layers_forward(E, T, nullptr, ws + r.valid, ws + r.enc_base, w, st, listed));
-  return PS_OK;
+  EncFwdOpts o;
+  o.rows_listed = listed;
+  return enc_layers_forward(E, T, nullptr, ws + r.valid, ws + r.enc_base, w, st, o);
 }
 
 extern "C" int ps_rtm_forward(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
@@ -2039,17 +2037,8 @@ extern "C" int ps_rtm_review_embeddings(const PsRtmDesc* desc, const PsRtmTensor
 }
 
 static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
-                             const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev, ps_stream_t stream);
-extern "C" int ps_rtm_backward(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
-                               const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev,
-                               ps_stream_t stream) {
-  const int rc = rtm_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream);
-  if (rc != PS_OK) { side_abort(); enc_clear_call_flags(); }    // never leave the side stream waiting behind a failed call (tem.hip)
-  return rc;
-}
-static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
-                             const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev, ps_stream_t stream) {
-  enc_clear_call_flags();
+                             const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev, ps_stream_t stream,
+                             EncBwdOut& out) {
   PS_REQUIRE(desc && params && batch && ws && grads, "rtm backward: null argument");
   const PsRtmDesc& D = *desc;
   RtmWs r; Ws w; PsTemDesc E; RtmK k;
@@ -2117,8 +2106,10 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   }
   const int eb = rtm_slot_blocks(r);
   if (k.pvc || k.det) k.gs = ws + r.enc_base + w.dx;     // (det + pv encoder: the review rows' gradients are parked in place, scattered below)
-  TRY(enc_layers_backward(E, T, TG, nullptr, ws + r.valid, ws + r.enc_base, w, st, &fold, nullptr, rtm_rows_listed(r, w)));
-  PS_REQUIRE(!enc_take_dx_two_partials(), "rtm backward: the encoder left d x as two partials, which nothing here adds");
+  EncBwdIn in;
+  in.fold = &fold; in.rows_listed = rtm_rows_listed(r, w);
+  TRY(enc_layers_backward(E, T, TG, nullptr, ws + r.valid, ws + r.enc_base, w, st, in, out));
+  PS_REQUIRE(!out.dx_two_partials, "rtm backward: the encoder left d x as two partials, which nothing here adds");
   if (D.review_encoder == PS_RENC_FS) {
     // through the review projection: d pre = dx * tanh', bias gradient, weight gradient, d raw = d pre . f_W
     PS_REQUIRE(G.rev_fs_w && G.rev_fs_b && params->rev_fs_w, "rtm backward: null review-encoder f_W gradient");
@@ -2264,4 +2255,14 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   TRY(launch_embed_scatter(e, st));
   TRY(side_join(st));
   return PS_OK;
+}
+
+extern "C" int ps_rtm_backward(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
+                               const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev,
+                               ps_stream_t stream) {
+  EncBwdOut out;
+  const int rc = rtm_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream, out);
+  enc_record_backward(out);
+  if (rc != PS_OK) side_abort();    // never leave the side stream waiting behind a failed call (tem.hip)
+  return rc;
 }

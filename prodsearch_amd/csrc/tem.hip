@@ -463,8 +463,8 @@ struct SideCtx {
 // mutex.  A context serves ONE host thread at a time — the single-thread contract of the step (include/prodsearch_hip.h,
 // "Threading"): the loader's prefetch thread never calls into this library's device side.
 #include <mutex>
+#include <utility>
 #define PS_MAX_DEVICES 16
-static bool env_on(const char* name) { const char* e = getenv(name); return e && *e && atoi(e) != 0; }
 // Anything that lets only ONE kernel run on the device at a time deadlocks a stream wait-value (the runtime implements it
 // as a one-thread kernel spinning on the word: the producer never gets to run).  Known serialisers: counter-collecting
 // profilers (rocprofv3 / rocprof --pmc), AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING / CUDA_LAUNCH_BLOCKING, debuggers
@@ -472,7 +472,7 @@ static bool env_on(const char* name) { const char* e = getenv(name); return e &&
 static bool dispatch_may_be_serialised() {
   static const char* const truthy[] = {"AMD_SERIALIZE_KERNEL", "AMD_SERIALIZE_COPY", "HIP_LAUNCH_BLOCKING",
                                        "CUDA_LAUNCH_BLOCKING", "HSA_ENABLE_DEBUG"};
-  for (const char* n : truthy) if (env_on(n)) return true;
+  for (const char* n : truthy) if (ps_env_int(n, 0) != 0) return true;
   const char* mq = getenv("GPU_MAX_HW_QUEUES");
   if (mq && *mq && atoi(mq) == 1) return true;          // one hardware queue: both streams share it in order
   // a profiling / tracing tool is attached: value waits only in the one mode known to keep dispatches concurrent — a
@@ -556,7 +556,7 @@ static SideCtx* side_ctx() {
   int& state = states[dev];
   if (state == 0) {
     state = -1;
-    if (!env_on("PS_NO_SIDE")) {
+    if (ps_env_int("PS_NO_SIDE", 0) == 0) {
       // the side stream carries filler (weight gradients, table scatters): LOWEST priority, so that when both streams have
       // workgroups ready the dependent chain of the main stream is dispatched first (PS_SIDE_PRIO=0: default priority)
       static const bool low_prio = ps_diag_int("PS_SIDE_PRIO", 1) != 0;
@@ -577,7 +577,7 @@ static SideCtx* side_ctx() {
       // does a stream that is being captured into a graph (side_fork / side_join check), and so does any environment
       // in which dispatches may be serialised (dispatch_may_be_serialised: the value wait would never return).
       int can_wait = 0;
-      const bool want = !env_on("PS_SIDE_EVENTS") && !dispatch_may_be_serialised();
+      const bool want = ps_env_int("PS_SIDE_EVENTS", 0) == 0 && !dispatch_may_be_serialised();
       if (ok && want &&
           hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, dev) == hipSuccess && can_wait) {
         if (hipMalloc((void**)&ctx.flag, 2 * sizeof(uint32_t)) != hipSuccess || hipMemset(ctx.flag, 0, 2 * sizeof(uint32_t)) != hipSuccess)
@@ -771,46 +771,22 @@ static int side_fork_injected_failure() {
   return PS_OK;
 }
 
-// does the (one-layer) encoder walk the valid-row list?  Then the rows of x at padded positions are never read, forward
-// or backward (K / V products, attention and their gradients all go through the list), and need not be written.
-bool enc_rowlist_taken(const PsTemDesc& D, const Ws& w, bool rows_listed) {
-  static const bool rows_on = ps_env_int("PS_NO_ROWLIST", 0) == 0;
-  if (!(rows_on && rows_listed && D.n_layers == 1 && w.qpos == 0 && w.vrows != 0 && w.S <= 64)) return false;
-  const LayerWs& l = w.layer[0];
-  if (l.Sq != 1 || l.n_in != D.B) return false;
-  AttnArgs probe;
-  memset(&probe, 0, sizeof(probe));
-  probe.Sq = 1; probe.S = w.S; probe.d = D.d; probe.H = D.H;
-  return attn_sq1_fits(probe);
-}
-
-// Decisions handed from one call to the next of the same entry point; cleared at every entry point and on its error returns
-static thread_local bool g_dx_two_partials = false;      // set by enc_layers_backward for the embed backward that follows it
-static thread_local bool g_split_bwd_deferred = false;   // encode_forward -> enc_layers_forward: the fused projection + attention launch re-splits the backward's streams
-void enc_clear_call_flags() { g_dx_two_partials = false; g_split_bwd_deferred = false; }
-bool enc_take_dx_two_partials() {
-  const bool two = g_dx_two_partials;
-  g_dx_two_partials = false;
-  return two;
-}
-// the predicate of enc_layers_forward's fused projection + attention launch, from what encode_forward knows before the embed launch
-static bool kvq_fwd_will_fuse(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed) {
-  if (D.model != PS_MODEL_TEM || D.n_layers != 1 || !ps_fusion_enabled()) return false;
-  const LayerWs& l = w.layer[0];
-  const WSplit kvs = make_wsplit(D, P, ws, w);
+// the shape part of layer i's attention arguments — all that the attn_*_fits predicates read —, dividers filled
+static AttnArgs attn_shape(const PsTemDesc& D, const Ws& w, int i, const int64_t* ui, const float* valid) {
+  const LayerWs& l = w.layer[i];
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.n_in = l.n_in; a.fan = l.fan; a.H = D.H; a.S = w.S; a.Sq = l.Sq; a.d = D.d; a.dh = D.d / (D.H > 0 ? D.H : 1); a.qpos = w.qpos;
-  a.seq_div = l.n_in / D.B; a.L = D.L; a.P = D.product_size;
+  a.seq_div = l.n_in / D.B; a.L = D.L; a.P = D.product_size; a.ui = ui; a.valid = valid;
+  a.qscale = 1.f / sqrtf((float)a.dh);
   attn_finish(a);
-  return kvs.on && kvs.fwd_kv && enc_rowlist_taken(D, w, rows_listed) && attn_sq1_fits(a) && a.fan > 1 && attn_wf_fits(a) &&
-         kvq_attn_fits(a) && l.amask;
+  return a;
 }
+
 int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
-                       const Ws& w, hipStream_t st, bool rows_listed, const ScoreArgs* fold_sc) {
-  const int B = D.B, d = D.d, S = w.S, NL = D.n_layers;
-  const float qscale = 1.f / sqrtf((float)(d / (D.H > 0 ? D.H : 1)));
-  bool fused_final = false;
+                       const Ws& w, hipStream_t st, const EncFwdOpts& o) {
+  const int d = D.d, S = w.S, NL = D.n_layers;
+  const EncPlan pl = enc_plan(D, P, ws, w, o.rows_listed, valid);
   for (int i = 0; i < NL; ++i) {
     const LayerWs& l = w.layer[i];
     const PsLayerTensors& Lp = P.layer[i];
@@ -824,28 +800,18 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       TRY(launch_ln_fwd(a, st));
     }
     const float* xn = ws + l.xn;
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_in = l.n_in; a.fan = l.fan; a.H = D.H; a.S = S; a.Sq = l.Sq; a.d = d; a.dh = d / D.H; a.qpos = w.qpos;
-    a.seq_div = l.n_in / B; a.L = D.L; a.P = D.product_size; a.ui = ui; a.valid = valid;
+    AttnArgs a = attn_shape(D, w, i, ui, valid);
     a.kp = ws + l.kp; a.vp = ws + l.vp; a.qp = ws + l.qp; a.attn = ws + l.attn; a.ctx = ws + l.ctx;
     a.drop = make_drop(D, PS_SITE_ATTN(i));
-    a.qscale = qscale;
-    attn_finish(a);
-    // One layer, replicas, d = 128: projections + attention of the one consumed position in ONE launch, a workgroup per
-    // sequence (kvq_attn_fwd_kernel): the K / V weight fragments were re-split by the embed launch in front (WSplit::fwd_kv)
-    const WSplit kvs = (i == 0 && NL == 1) ? make_wsplit(D, P, ws, w) : WSplit{};
-    const bool kvq_fused = i == 0 && NL == 1 && kvs.on && kvs.fwd_kv && ps_fusion_enabled() && enc_rowlist_taken(D, w, rows_listed) &&
-                           attn_sq1_fits(a) && a.fan > 1 && attn_wf_fits(a) && kvq_attn_fits(a) && l.amask;
-    PS_REQUIRE(kvq_fused || !g_split_bwd_deferred, "forward: the embed launch left the backward's weight streams to a launch that is not coming");
-    if (kvq_fused) {
+    uint32_t* amask = reinterpret_cast<uint32_t*>(ws + l.amask);
+    if (pl.attn[i] == ATTN_KVQ) {
+      const WSplit kvs = make_wsplit(D, P, ws, w);
       KvqArgs q;
       memset(&q, 0, sizeof(q));
-      if (g_split_bwd_deferred) q.split = kvs;       // the backward-only streams, left out of the embed launch (encode_forward)
-      g_split_bwd_deferred = false;
+      if (o.split_bwd_left) q.split = kvs;           // the backward-only streams, left out of the embed launch (encode_forward)
       q.at = a; q.x = xn; q.kv_stream = kvs.fwd_kv;
       q.bk = Lp.bk; q.bv = Lp.bv; q.wq = Lp.wq; q.bq = Lp.bq;
-      q.kp = ws + l.kp; q.vp = ws + l.vp; q.qp = ws + l.qp; q.amask = reinterpret_cast<uint32_t*>(ws + l.amask);
+      q.kp = ws + l.kp; q.vp = ws + l.vp; q.qp = ws + l.qp; q.amask = amask;
       TRY(launch_kvq_attn_fwd(q, st));
     } else {   // K, V, Q projections (neural.py:192-197), Q pre-divided by sqrt(dh) (:206)
       GemmGroup g;
@@ -855,23 +821,24 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       g.p[1] = gp(xn, d, 0, Lp.wv, d, 0, ws + l.vp, d, ns, d, d); g.p[1].bias = Lp.bv;
       if (l.Sq == S) g.p[2] = gp(xn, d, 0, Lp.wq, d, 0, ws + l.qp, d, ns, d, d);
       else g.p[2] = gp(xn + (size_t)w.qpos * d, S * d, 0, Lp.wq, d, 0, ws + l.qp, d, l.n_in, d, d);
-      g.p[2].bias = Lp.bq; g.p[2].alpha = qscale;
+      g.p[2].bias = Lp.bq; g.p[2].alpha = a.qscale;
       // valid rows only (EmbedArgs::vrows): the K / V rows of padded positions are never read (sq1_load zero-fills them)
-      if (i == 0 && enc_rowlist_taken(D, w, rows_listed)) {
+      if (pl.rowlist) {
         const int32_t* vr = reinterpret_cast<const int32_t*>(ws + w.vrows);
         const int32_t* vc = reinterpret_cast<const int32_t*>(ws + w.vcount);
         g.p[0].ridx = vr; g.p[0].rcount = vc;
         g.p[1].ridx = vr; g.p[1].rcount = vc;
       }
       TRY(ps_launch_gemm(g, st));
+      switch (pl.attn[i]) {
+        case ATTN_WF: TRY(launch_attn_fwd_wf(a, amask, st)); break;
+        case ATTN_W1: TRY(launch_attn_fwd_w1(a, st)); break;
+        case ATTN_SQ1: TRY(launch_attn_fwd_sq1(a, st)); break;
+        default: TRY(launch_attn_fwd(a, st));
+      }
     }
-    if (kvq_fused) { }
-    else if (attn_sq1_fits(a) && a.fan > 1 && attn_wf_fits(a)) TRY(launch_attn_fwd_wf(a, reinterpret_cast<uint32_t*>(ws + l.amask), st));
-    else if (attn_sq1_fits(a) && attn_w1_fits(a)) TRY(launch_attn_fwd_w1(a, st));
-    else TRY(attn_sq1_fits(a) ? launch_attn_fwd_sq1(a, st) : launch_attn_fwd(a, st));
-    const bool fuse = ps_fusion_enabled() && i == NL - 1 && l.Sq == 1 && mlp_fused_serves(d, D.F) && w.wsplit &&
-                      P.final_ln_g && P.final_ln_b;
-    PS_REQUIRE(!fold_sc || fuse || i != NL - 1, "forward: folded scoring without the fused last layer");   // (earlier layers: never fused)
+    const bool fuse = pl.fwd_fuse_last && i == NL - 1;
+    PS_REQUIRE(!o.fold_sc || fuse || i != NL - 1, "forward: folded scoring without the fused last layer");   // (earlier layers: never fused)
     if (fuse) {   // Wo + LN + W1 + GELU + W2 + final LN of the last layer in one kernel (mlp_fused.hip)
       MlpFwdArgs m;
       memset(&m, 0, sizeof(m));
@@ -883,10 +850,9 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       m.drop_ff2 = make_drop(D, PS_SITE_FF2(i));
       m.y1 = ws + l.y1; m.ln1 = ws + l.ln1; m.st1 = ws + l.ff_stats; m.a1 = ws + l.a1; m.h1 = ws + l.h1;
       m.y2 = ws + l.y2; m.stf = ws + w.fin_stats; m.enc = ws + w.enc;
-      if (fold_sc) { m.fold_score = 1; m.sc = *fold_sc; }
+      if (o.fold_sc) { m.fold_score = 1; m.sc = *o.fold_sc; }
       m.x3 = make_wsplit(D, P, ws, w);
       TRY(launch_mlp_fwd_fused(m, st));
-      fused_final = true;
       continue;
     }
     {   // final_linear + dropout + residual (neural.py:228-231, transformer.py:56)
@@ -908,7 +874,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       TRY(run1(p2, st));
     }
   }
-  if (fused_final) return PS_OK;
+  if (pl.fwd_fuse_last) return PS_OK;
   // final LayerNorm (transformer.py:86) on the consumed position only
   PS_REQUIRE(P.final_ln_g && P.final_ln_b, "forward: null final LayerNorm");
   LnFwdArgs f;
@@ -917,7 +883,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
     f = LnFwdArgs{ws + l.y2, d, ws + w.enc, d, ws + w.fin_stats, P.final_ln_g, P.final_ln_b, w.Mf, d, 1e-6f};
   } else {
     f = LnFwdArgs{ws + w.x + (size_t)w.qpos * d, S * d, ws + w.enc, d, ws + w.fin_stats, P.final_ln_g,
-                  P.final_ln_b, B, d, 1e-6f};
+                  P.final_ln_b, D.B, d, 1e-6f};
   }
   TRY(launch_ln_fwd(f, st));
   return PS_OK;
@@ -930,19 +896,10 @@ struct SamplerArgs { const float* prob; const int32_t* alias; int64_t* items; in
 // (B^2 L / 2 index reads in total): fine up to a few thousand sequences, dense products beyond
 static bool rows_list_ok(const PsTemDesc& D) { return D.L <= 64 && (int64_t)D.B * D.B * D.L <= ((int64_t)64 << 20); }
 
-static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
-                               hipStream_t st, const SamplerArgs* samp, const ScoreArgs* fold_sc);
 static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
                           hipStream_t st, const SamplerArgs* samp = nullptr, const ScoreArgs* fold_sc = nullptr) {
-  enc_clear_call_flags();
-  const int rc = encode_forward_impl(D, P, Bt, ws, w, st, samp, fold_sc);
-  if (rc != PS_OK) enc_clear_call_flags();
-  return rc;
-}
-static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
-                               hipStream_t st, const SamplerArgs* samp, const ScoreArgs* fold_sc) {
   const bool tem = D.model == PS_MODEL_TEM;
-  const int B = D.B, d = D.d, S = w.S, NL = tem ? D.n_layers : 0;
+  const int B = D.B, d = D.d, S = w.S;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
   PS_REQUIRE(P.word_emb && P.product_emb && hist, "forward: null embedding table");
   EmbedArgs e;
@@ -971,8 +928,11 @@ static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const 
   if (fs_fused) { e.fs_w = P.fs_w; e.fs_b = P.fs_b; }
   if (fold_sc) { e.fold_words = 1; e.sc = *fold_sc; }
   e.split = make_wsplit(D, P, ws, w);
-  g_split_bwd_deferred = e.split.on && D.training && kvq_fwd_will_fuse(D, P, ws, w, rows_list_ok(D));
-  e.split_fwd_only = g_split_bwd_deferred ? 1 : 0;
+  EncFwdOpts o;
+  o.rows_listed = rows_list_ok(D); o.fold_sc = fold_sc;
+  // the fused projection + attention launch re-splits the backward's streams
+  o.split_bwd_left = e.split.on && D.training && enc_plan(D, P, ws, w, o.rows_listed, nullptr).attn[0] == ATTN_KVQ;
+  e.split_fwd_only = o.split_bwd_left ? 1 : 0;
   TRY(launch_embed_fwd(e, st));
   if (e.fs && !fs_fused) {   // FSEncoder: tanh(f_W . mean + b)  (text_encoder.py:39); also writes row 0 of x (+pe[0])
     GemmProblem p = gp(ws + w.qmean, d, 0, P.fs_w, d, 0, ws + w.query_emb, d, B, d, d);
@@ -982,17 +942,12 @@ static int encode_forward_impl(const PsTemDesc& D, const PsTemTensors& P, const 
   }
   if (ps_model_attn(D.model)) return ae_forward(D, P, Bt.u_item_idxs, ws, w, st);
   if (!tem) return PS_OK;
-
-  return enc_layers_forward(D, P, Bt.u_item_idxs, nullptr, ws, w, st, rows_list_ok(D), fold_sc);
+  return enc_layers_forward(D, P, Bt.u_item_idxs, nullptr, ws, w, st, o);
 }
 
-// Folded scoring (ScoreArgs): TEM training forward with replicas whose last layer takes the wave-specialised fused form
-static bool can_fold_score(const PsTemDesc& D, const PsTemTensors& P, const Ws& w, hipStream_t st) {
-  if (D.model != PS_MODEL_TEM || D.n_layers < 1 || D.C != 0 || w.R != D.K + 1 || w.R < 2 || D.W < 1) return false;
-  const LayerWs& l = w.layer[D.n_layers - 1];
-  if (l.Sq != 1 || l.M2 != w.Mf || !P.final_ln_g || !P.final_ln_b) return false;
-  if (stream_capturing(st)) return false;            // graph replay patches the loss kernel's arguments: unfolded form
-  return mlp_fwd_can_fold_score(w.Mf, D.F, D.d);
+// Folded scoring (EncPlan::fold_score) — not on a capturing stream: graph replay patches the loss kernel's arguments (unfolded form)
+static bool can_fold_score(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, hipStream_t st) {
+  return enc_plan(D, P, ws, w, rows_list_ok(D), nullptr).fold_score && !stream_capturing(st);
 }
 static void fold_finish(const PsTemDesc& D, float* ws, const Ws& w, ScoreArgs& s, const SamplerArgs* samp) {
   s.word_blk = ws + w.word_blk; s.item_blk = ws + w.item_blk; s.ticket = reinterpret_cast<uint32_t*>(ws + w.ticket);
@@ -1032,7 +987,7 @@ extern "C" int ps_tem_forward(const PsTemDesc* desc, const PsTemTensors* params,
   ScoreArgs s;
   fill_score(D, *params, *batch, workspace, w, s);
   s.loss3 = loss3; s.loss_acc = loss_acc;
-  if (can_fold_score(D, *params, w, st)) {             // no gather+score / loss launches: see ScoreArgs, folded form
+  if (can_fold_score(D, *params, workspace, w, st)) {             // no gather+score / loss launches: see ScoreArgs, folded form
     fold_finish(D, workspace, w, s, nullptr);
     return encode_forward(D, *params, *batch, workspace, w, st, nullptr, &s);
   }
@@ -1063,7 +1018,7 @@ extern "C" int ps_tem_forward_sampled(const PsTemDesc* desc, const PsTemTensors*
   ScoreArgs s;
   fill_score(D, *params, Bt, workspace, w, s);
   s.loss3 = loss3; s.loss_acc = loss_acc;
-  if (can_fold_score(D, *params, w, st)) {
+  if (can_fold_score(D, *params, workspace, w, st)) {
     fold_finish(D, workspace, w, s, &samp);
     return encode_forward(D, *params, Bt, workspace, w, st, &samp, &s);
   }
@@ -1119,79 +1074,341 @@ extern "C" int ps_tem_encode(const PsTemDesc* desc, const PsTemTensors* params, 
 }
 
 // park the {dgamma, dbeta, colsum} column sums of one LN backward (see ColFoldList) when the caller collects them
+static float* park(ColFoldList* fold, float* partial, int nblk, int d, float* g0, float* g1, float* g2) {
+  ColFold& f = fold->e[fold->n++];
+  f.partial = partial; f.nblk = nblk; f.d = d;
+  f.dst[0] = g0; f.dst[1] = g1; f.dst[2] = g2;
+  return partial;
+}
 static void park_colsums(LnBwdArgs& a, float* ws, const Ws& w, ColFoldList* fold) {
   if (!fold || fold->n >= PS_MAX_COLFOLD) return;
-  ColFold& f = fold->e[fold->n];
-  a.partial = ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * a.d;
-  f.partial = a.partial; f.nblk = ln_bwd_blocks(a.rows); f.d = a.d;
-  f.dst[0] = a.dgamma; f.dst[1] = a.dbeta; f.dst[2] = a.colsum;
-  ++fold->n;
+  a.partial = park(fold, ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * a.d, ln_bwd_blocks(a.rows), a.d, a.dgamma, a.dbeta, a.colsum);
 }
 
-static int& fuse_bwd_min_slot() {
-  static int v = ps_env_int("PS_FUSE_BWD_MIN", 1024);
-  return v;
-}
-extern "C" int ps_set_fuse_bwd_min(int rows) {
-  const int old = fuse_bwd_min_slot();
-  fuse_bwd_min_slot() = rows;
-  return old;
-}
+static int& fuse_bwd_min_slot() { static int v = ps_env_int("PS_FUSE_BWD_MIN", 1024); return v; }
+extern "C" int ps_set_fuse_bwd_min(int rows) { return std::exchange(fuse_bwd_min_slot(), rows); }
 
 // The item rows' gradient scatter (g_product_emb[idx(b, j)] += ds * enc[(b, j)]) rides in the fused per-replica backward, which
 // holds ds and idx already, and the score backward's launch shrinks to its word tasks (MlpBwdArgs::g_product_emb,
 // ScoreArgs::items_elsewhere), which then are the main stream's last launch instead of the side stream's first (see
-// enc_layers_backward).  PS_ITEM_SCATTER_FUSED=0: the score backward's own item workgroups, on the side stream, as before.
+// bwd_fused_last).  PS_ITEM_SCATTER_FUSED=0: the score backward's own item workgroups, on the side stream, as before.
 // Deterministic mode never takes it (its sole-owner scatter walks the item tasks in order).
-static int& item_scatter_fused_slot() {
-  static int v = ps_env_int("PS_ITEM_SCATTER_FUSED", 1);
-  return v;
-}
-extern "C" int ps_set_item_scatter_fused(int on) {
-  const int old = item_scatter_fused_slot();
-  item_scatter_fused_slot() = on;
-  return old;
-}
+static int& item_scatter_fused_slot() { static int v = ps_env_int("PS_ITEM_SCATTER_FUSED", 1); return v; }
+extern "C" int ps_set_item_scatter_fused(int on) { return std::exchange(item_scatter_fused_slot(), on); }
 static int g_item_scatter_taken = 0;     // the last backward's fused kernel scattered the item rows
 extern "C" int ps_item_scatter_fused_taken(void) { return g_item_scatter_taken; }
+void enc_record_backward(const EncBwdOut& out) { g_item_scatter_taken = out.item_scatter_taken ? 1 : 0; }
 
-// K/V/Q weight gradients of the first layer that the caller launches on the main stream AFTER its embedding scatter
-// (PS_WG3_LAST, item transformer): the scatter (atomics) then shares the machine with the side stream's W2 / W1 / Wo
-// products, and these follow when those are nearly through, instead of slowing each other down product beside product
-static thread_local GemmProblem g_wg3_last[4];
-static thread_local int g_wg3_last_n = 0;
-static thread_local bool g_wg3_defer_ok = false;          // set by a caller that will flush them
-// ... and, when the fused backward has scattered the item rows, the score backward's word tasks behind them (see there)
-static thread_local bool g_score_words_last = false;
-static int flush_wg3_last(hipStream_t st) {
-  const int n = g_wg3_last_n;
-  g_wg3_last_n = 0;
-  return n ? run_wgrads(g_wg3_last, n, st) : PS_OK;
-}
-int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui,
-                        const float* valid, float* ws, const Ws& w, hipStream_t st, ColFoldList* fold,
-                        const ScoreArgs* score_on_side, bool rows_listed) {
-  const bool drop = D.training && D.dropout > 0.f;
-  const int B = D.B, d = D.d, S = w.S, NL = D.n_layers, F = D.F;
-  PS_REQUIRE(G.final_ln_g && G.final_ln_b, "backward: null final LayerNorm gradient");
-  // 2. final LayerNorm backward
-  LnBwdArgs f;
-  memset(&f, 0, sizeof(f));
-  f.dy = ws + w.denc; f.lddy = d; f.stats = ws + w.fin_stats; f.g = P.final_ln_g; f.d = d;
-  f.dgamma = G.final_ln_g; f.dbeta = G.final_ln_b;
+// The switches are read once, here; the setters' slots (ps_set_fuse_bwd_min, ps_set_item_scatter_fused, ps_set_deterministic)
+// on every call.
+EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed, const float* valid) {
+  static const bool rows_on = ps_env_int("PS_NO_ROWLIST", 0) == 0;
+  static const bool bwd_fuse_on = ps_env_int("PS_NO_FUSE_BWD", 0) == 0;
+  static const bool dx_fused_on = ps_env_int("PS_KVDX_FUSED", 1) != 0;
+  static const bool wgrad_early = ps_diag_int("PS_WGRAD_LATE", 0) == 0;
+  static const int wg3_side = ps_diag_int("PS_WG3_SIDE", -1);
+  static const bool wg3_main_on = wg3_side >= 0 ? wg3_side == 0 : fork_by_kernel();
+  static const bool wg3_last = ps_diag_int("PS_WG3_LAST", 1) != 0;
+  EncPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  const int NL = D.n_layers, d = D.d, S = w.S;
+  if (D.model != PS_MODEL_TEM || NL < 1) return pl;
+  AttnArgs a0;                                           // (ends as layer 0's)
+  for (int i = NL - 1; i >= 0; --i) {
+    a0 = attn_shape(D, w, i, nullptr, valid);
+    pl.attn[i] = !attn_sq1_fits(a0) ? ATTN_GENERIC : a0.fan > 1 && attn_wf_fits(a0) ? ATTN_WF : attn_w1_fits(a0) ? ATTN_W1 : ATTN_SQ1;
+  }
+  const LayerWs& l0 = w.layer[0];
+  const LayerWs& ll = w.layer[NL - 1];
+  const bool sq1 = pl.attn[0] != ATTN_GENERIC, wf = pl.attn[0] == ATTN_WF, w1 = wf || pl.attn[0] == ATTN_W1;
+  const bool qall = l0.Sq == S;
+  const WSplit kvs = make_wsplit(D, P, ws, w);           // (fwd_kv / bwd_kv: one-layer encoders only)
+  pl.rowlist = rows_on && rows_listed && NL == 1 && w.qpos == 0 && w.vrows != 0 && l0.n_in == D.B && sq1;
+  // One layer, replicas, d = 128: projections + attention of the one consumed position in ONE launch, a workgroup per
+  // sequence (kvq_attn_fwd_kernel): the K / V weight fragments were re-split by the embed launch in front (WSplit::fwd_kv)
+  if (NL == 1 && kvs.on && kvs.fwd_kv && ps_fusion_enabled() && pl.rowlist && wf && kvq_attn_fits(a0) && l0.amask) pl.attn[0] = ATTN_KVQ;
+  const bool last_fusable = ps_fusion_enabled() && ll.Sq == 1 && mlp_fused_serves(d, D.F) && w.wsplit;
+  pl.fwd_fuse_last = last_fusable && P.final_ln_g && P.final_ln_b;
+  // Folded scoring (ScoreArgs): TEM training forward with replicas whose last layer takes the wave-specialised fused form
+  pl.fold_score = pl.fwd_fuse_last && D.C == 0 && w.R == D.K + 1 && w.R >= 2 && D.W >= 1 && ll.M2 == w.Mf &&
+                  mlp_fwd_can_fold_score(w.Mf, D.F, d);
+  EncPlan::Bwd& b = pl.bwd;
   // The last layer's whole per-replica backward (final LN, FFN, FF LN, Wo) as one kernel (mlp_fused.hip) when the
   // forward took the fused form too; needs parked column sums (fold) and one parked row per workgroup (Ws::lnrows of them).
+  b.fuse_last = last_fusable && bwd_fuse_on && ll.M2 == w.Mf && w.Mf >= fuse_bwd_min_slot() && mlp_bwd_fused_blocks(w.Mf) <= w.lnrows;
+  b.item_scatter = b.fuse_last && item_scatter_fused_slot() != 0 && !ps_deterministic();
+  b.wg3_main = b.fuse_last && wg3_main_on && ll.n_in * S <= 2 * ll.M2;   // (review transformer: 78k K/V rows vs 1.5k replica rows -> side)
+  b.wg3_last = b.wg3_main && wg3_last && NL == 1;
+  b.wgrad_early = wgrad_early;
+  // first layer, one query row per sequence, d == 128: dQ.Wq rides in the attention backward's tail (two partial
+  // rows per sequence in the free d ln1 buffer) instead of a [n_in,128]x[128,128] GEMM launch of its own
+  b.q_folded = sq1 && !qall && ps_fusion_enabled() &&
+               (w1 ? (!wf || d == 128) && (size_t)(wf ? 2 : 1) * l0.n_in <= (size_t)l0.M2
+                   : d == 128 && attn_sq1_split(a0) == 2 && (size_t)2 * l0.n_in <= (size_t)l0.M2);
+  // valid rows only: padded positions have exactly-zero dK / dV rows (their attention weights are 0), never read and never
+  // written: the K/V weight gradients (and the dX product) run over the batch's row list instead of all n_in*S rows
+  b.listed = pl.rowlist && !qall;
+  // ... and, one-layer encoder with replicas: so does the K / V input gradient itself (AttnArgs::kvb_stream) — no dX GEMM launch
+  // on the dependent chain; the embed scatter adds the two head groups' partial rows (EmbedBwdArgs::dx2)
+  // (FS query encoder only: its fused backward reads d query_emb as the two partials; the AVG branch copies one row of dx)
+  b.dx_fused = dx_fused_on && wf && b.q_folded && b.listed && d == 128 && kvs.on && kvs.bwd_kv && !ps_deterministic() &&
+               attn_bwd_wf_two_partials(a0) && D.query_encoder == PS_QENC_FS;
+  // round 4: where dQ.Wq is NOT folded (d != 128: the C5 shard) the replicas' fan-in is summed by a launch of its own
+  // (launch_fanin_sum) so that the dX product can still run over the row list: 133 -> ~50 us at C5
+  b.presum = b.listed && !b.q_folded && l0.fan > 1 && (d % 4) == 0;
+  return pl;
+}
+
+// What the three sequences of the encoder backward share
+struct EncBwd {
+  const PsTemDesc& D; const PsTemTensors& P; const PsTemTensors& G; float* ws; const Ws& w; hipStream_t st;
+  const EncPlan& pl; const EncBwdIn& in; EncBwdOut& out;
+  bool drop() const { return D.training && D.dropout > 0.f; }
+  const float* do2() const { return drop() ? ws + w.do2 : ws + w.dy2; }     // d y2 behind the FF2 dropout
+  const float* dout() const { return drop() ? ws + w.do_ : ws + w.dy1; }    // d y1 behind the context dropout
+  GemmProblem wgrad_w2(int i) const { return gp_wgrad(do2(), D.d, ws + w.layer[i].h1, D.F, G.layer[i].w2, D.d, D.F, w.layer[i].M2); }
+  GemmProblem wgrad_w1(int i) const { return gp_wgrad(ws + w.da1, D.F, ws + w.layer[i].ln1, D.d, G.layer[i].w1, D.F, D.d, w.layer[i].M2); }
+  GemmProblem wgrad_wo(int i) const { return gp_wgrad(dout(), D.d, ws + w.layer[i].ctx, D.d, G.layer[i].wo, D.d, D.d, w.layer[i].M2); }
+};
+
+// The last layer's per-replica backward as one kernel: final LN, FFN, FF LN, Wo (EncPlan::Bwd::fuse_last).  `score`: d enc from
+// the scores inside the kernel, the rest of the score backward placed here.
+static int bwd_fused_last(const EncBwd& c, const ScoreArgs* score) {
+  const PsTemDesc& D = c.D; const Ws& w = c.w; float* ws = c.ws; hipStream_t st = c.st;
+  const int i = D.n_layers - 1, d = D.d, F = D.F, M2 = w.layer[i].M2;
+  const LayerWs& l = w.layer[i];
+  const PsLayerTensors& Lp = c.P.layer[i];
+  const PsLayerTensors& Lg = c.G.layer[i];
+  ColFoldList* fold = c.in.fold;
+  PS_REQUIRE(fold && fold->n + 3 <= PS_MAX_COLFOLD, "backward: the fused last layer parks three column sums with its caller");
+  MlpBwdArgs m;
+  memset(&m, 0, sizeof(m));
+  m.M = M2; m.F = F;
+  m.denc = ws + w.denc; m.y2 = ws + l.y2; m.stf = ws + w.fin_stats; m.gf = c.P.final_ln_g;
+  m.y1 = ws + l.y1; m.st1 = ws + l.ff_stats; m.g1 = Lp.ff_ln_g; m.a1 = ws + l.a1;
+  m.wo = Lp.wo; m.w1 = Lp.w1; m.w2 = Lp.w2;
+  m.drop_ctx = make_drop(D, PS_SITE_CTX(i)); m.drop_ff1 = make_drop(D, PS_SITE_FF1(i));
+  m.drop_ff2 = make_drop(D, PS_SITE_FF2(i));
+  if (score) {   // d enc from the scores (see MlpBwdArgs::item_scores)
+    const ScoreArgs& sa = *score;
+    m.item_scores = sa.item_scores; m.target = sa.target; m.neg_items = sa.neg_items; m.product_emb = sa.product_emb;
+    m.B = sa.B; m.K = sa.K; m.pos_weight = sa.pos_weight; m.P = sa.P; m.scale = sa.scale; m.scale_dev = sa.scale_dev;
+    if (c.pl.bwd.item_scatter && c.in.caller_flushes_tail && sa.part == 0 && sa.enc && sa.g_product_emb) {
+      m.enc = sa.enc; m.g_product_emb = sa.g_product_emb;
+      m.g_product_bias = sa.bias_product ? sa.g_product_bias : nullptr;
+    }
+  }
+  m.x3 = make_wsplit(D, c.P, ws, w);                 // the fragment streams the forward's embed launch left in the workspace
+  m.do2 = const_cast<float*>(c.do2()); m.da1 = ws + w.da1; m.dy1 = ws + w.dy1;
+  m.dout = const_cast<float*>(c.dout()); m.dctx = ws + w.dctx;
+  const int nwg = mlp_bwd_fused_blocks(M2);
+  // parked column sums: {final LN gamma, beta, b2}, {FF LN gamma, beta, bo}, {b1}
+  m.part_f = park(fold, ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * d, nwg, d, c.G.final_ln_g, c.G.final_ln_b, Lg.b2);
+  m.part_1 = park(fold, ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * d, nwg, d, Lg.ff_ln_g, Lg.ff_ln_b, Lg.bo);
+  m.part_b1 = park(fold, ws + w.gcpart, mlp_bwd_b1_rows(M2, F), F, Lg.b1, nullptr, nullptr);
+  // (measured and dropped: the table scatter of the score backward — it needs nothing of this backward — started beside
+  // the fused kernel below, its fork carried by that kernel: starved by 252 workgroups that own their CUs' LDS it took
+  // 74 us instead of 29 and slowed the attention backward behind it, 0.278 -> 0.282 ms/step)
+  TRY(launch_mlp_bwd_fused(m, st));
+  TRY(side_fork(st));                           // fork 1: W2, W1, Wo weight gradients under the attention backward
+  if (score && m.g_product_emb) {
+    // the fused kernel above has added the item rows: what is left of the score backward are its word tasks (2 B workgroups,
+    // 14 us alone at C2).  Leading the side stream, as the whole scatter does below, they only moved the W2 / W1 / Wo group
+    // into the attention backward and the embedding scatter (42 -> 52-58 us, the side stream still the last to end: a wash);
+    // the caller launches them as the main stream's LAST kernel instead, behind its K / V / Q weight gradients — the main
+    // stream ended 12 us before the side stream, which now carries the group alone, and the join's value is there when the
+    // main stream arrives (C2 0.2133 -> 0.2067 ms/step, profiles/item_scatter_fused_notes.md)
+    c.out.score_words_last = true;
+    c.out.item_scatter_taken = true;
+  } else if (score) {                           // ... led by the table scatter of the score backward (behind them instead: 0.284 -> 0.293 ms/step)
+    ScoreArgs t = *score;
+    t.denc = nullptr;
+    SideCtx* sc = side_ctx_on(st);
+    TRY(launch_score_bwd(t, sc ? sc->stream : st));
+  }
+  // (a second side stream for W1 / Wo beside W2 measured 0.389 vs 0.368 ms: slower)
+  // one launch for the three (the flat group form: every member keeps its own split count; three launches of ~250
+  // latency-bound workgroups one after the other took 86 us at C2; review transformer 0.563 -> 0.543 ms/step, C2 0.3156 ->
+  // 0.3144).  PS_WGRAD_GROUP_ROWS=0 restores the separate launches.
+  static const int wg_group_rows = ps_diag_int("PS_WGRAD_GROUP_ROWS", (1 << 30));
+  GemmProblem all3[3] = {c.wgrad_w2(i), c.wgrad_w1(i), c.wgrad_wo(i)};
+  if (M2 <= wg_group_rows) return side_run(all3, 3, st);
+  for (int q = 0; q < 3; ++q) TRY(side_run(all3 + q, 1, st));
+  return PS_OK;
+}
+
+// Layer i's FFN, FF LayerNorm and Wo backward as launches of their own: d y2 -> d ctx
+static int bwd_ffn(const EncBwd& c, int i) {
+  const PsTemDesc& D = c.D; const Ws& w = c.w; float* ws = c.ws; hipStream_t st = c.st;
+  const int d = D.d, F = D.F, M2 = w.layer[i].M2;
+  const LayerWs& l = w.layer[i];
+  const PsLayerTensors& Lp = c.P.layer[i];
+  const PsLayerTensors& Lg = c.G.layer[i];
+  ColFoldList* fold = c.in.fold;
+  GemmProblem p = gp(c.do2(), d, 0, Lp.w2, F, 1, ws + w.da1, F, M2, F, d);      // d h1 = do2 . W2
+  p.act = ACT_GELU_BWD; p.act_aux = ws + l.a1; p.drop = make_drop(D, PS_SITE_FF1(i)); p.colsum = Lg.b1;
+  if (fold && fold->n < PS_MAX_COLFOLD && i == D.n_layers - 1)      // park the b1 column sums (one buffer: last layer only)
+    p.colsum_part = park(fold, ws + w.gcpart, 4 * ps_cdiv(M2, 64), F, Lg.b1, nullptr, nullptr);
+  TRY(run1(p, st));
+  // dW2 += do2^T . h1 and dW1 += da1^T . ln1 are launched further down, once the dX chain of the MLP is through
+  // (beside it they slowed every link: 44 vs 33 us for the GEMM below); they then share the machine with the
+  // attention backward and the big dX GEMM instead.  Measured a wash in step time (both orders 0.509 ms): the
+  // backward is throughput-bound once both streams are busy.
+  GemmProblem wg[1] = {c.wgrad_w2(i)};
+  GemmProblem wg1[1] = {c.wgrad_w1(i)};
+  GemmProblem q = gp(ws + w.da1, F, 0, Lp.w1, d, 1, ws + w.dln1, d, M2, d, F);  // d ln1 = da1 . W1
+  TRY(run1(q, st));
+  // fork 1: the two big weight gradients (W2, W1) start as soon as d a1 exists, under the LN backward, the Wo dX
+  // GEMM and the attention backward.  (Forked one GEMM later, behind d ctx, the side stream's 112 us of weight
+  // gradients ended 13 us after the main chain and the step paid a late join on top.)
+  if (c.pl.bwd.wgrad_early) {
+    TRY(side_fork(st));
+    TRY(side_run(wg, 1, st));
+    TRY(side_run(wg1, 1, st));
+  }
+  LnBwdArgs n;
+  memset(&n, 0, sizeof(n));
+  n.dy = ws + w.dln1; n.lddy = d; n.x = ws + l.y1; n.ldx = d; n.stats = ws + l.ff_stats; n.g = Lp.ff_ln_g;
+  n.rows = M2; n.d = d;
+  n.res.mode = RES_DIRECT; n.res.ptr = ws + w.dy2; n.res.ld = d;            // residual  output + x
+  n.dx = ws + w.dy1; n.lddx = d;
+  if (c.drop()) { n.out2 = ws + w.do_; n.drop2 = make_drop(D, PS_SITE_CTX(i)); }
+  n.colsum = Lg.bo; n.dgamma = Lg.ff_ln_g; n.dbeta = Lg.ff_ln_b;
+  park_colsums(n, ws, w, fold);
+  TRY(launch_ln_bwd(n, st));
+  GemmProblem pc = gp(c.dout(), d, 0, Lp.wo, d, 1, ws + w.dctx, d, M2, d, d);    // d ctx = do . Wo
+  TRY(run1(pc, st));
+  if (!c.pl.bwd.wgrad_early) {
+    GemmProblem wgo[1] = {c.wgrad_wo(i)};
+    TRY(side_fork(st));                         // fork 1 (late form): W2, W1, Wo weight gradients under the attention backward
+    TRY(side_run(wg, 1, st));
+    TRY(side_run(wg1, 1, st));
+    TRY(side_run(wgo, 1, st));
+  }
+  return PS_OK;
+}
+
+// Layer i's attention backward, the K / V / Q weight gradients and the input gradient d xn = dK.Wk + dV.Wv (+ dQ.Wq).
+// `fused`: bwd_fused_last ran in front (the side stream holds W2 / W1 / Wo), not bwd_ffn.
+static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, const float* valid) {
+  const PsTemDesc& D = c.D; const Ws& w = c.w; float* ws = c.ws; hipStream_t st = c.st;
+  const EncPlan::Bwd& pb = c.pl.bwd;
+  const int d = D.d, S = w.S;
+  const LayerWs& l = w.layer[i];
+  const PsLayerTensors& Lp = c.P.layer[i];
+  const PsLayerTensors& Lg = c.G.layer[i];
+  const float* xn = ws + l.xn;
+  const int ns = l.n_in * S;
+  ColFoldList* fold = c.in.fold;
+  AttnArgs a = attn_shape(D, w, i, ui, valid);
+  a.kp = ws + l.kp; a.vp = ws + l.vp; a.qp = ws + l.qp; a.attn = ws + l.attn;
+  a.drop = make_drop(D, PS_SITE_ATTN(i));
+  a.dctx = ws + w.dctx;
+  const bool qall = l.Sq == S;
+  a.lddkv = qall ? 3 * d : 2 * d;
+  a.dkv = ws + w.dkv;
+  a.dq = qall ? ws + w.dkv + 2 * d : ws + w.dq;
+  a.lddq = qall ? 3 * d : d;
+  a.dbq = Lg.bq; a.dbk = Lg.bk; a.dbv = Lg.bv;
+  const AttnForm form = c.pl.attn[i];
+  const bool wf = form == ATTN_WF || form == ATTN_KVQ;   // one wave per (sequence, four heads), replicas inside
+  const bool w1 = wf || form == ATTN_W1;                 // one wave per sequence (no replicas)
+  if (form != ATTN_GENERIC && fold && fold->n < PS_MAX_COLFOLD)   // bias gradients: one parked row per sequence instead of n_in same-address atomics per column
+    a.bias_part = park(fold, ws + w.abpart + (size_t)i * w.layer[D.n_layers - 1].n_in * 3 * d, l.n_in, d, Lg.bq, Lg.bk, Lg.bv);
+  // the first layer's forms (EncPlan::Bwd); listed / presum / dx_fused: one-layer encoders only
+  const bool q_folded = i == 0 && pb.q_folded, listed = pb.listed, presum = pb.presum, dx_fused = pb.dx_fused;
+  if (q_folded) { a.wq = Lp.wq; a.dxq_part = ws + w.dln1; a.fanin_src = ws + w.dy1; }
+  if (dx_fused) { a.kvb_stream = make_wsplit(D, c.P, ws, w).bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; }
+  c.out.dx_two_partials = dx_fused;
+  const bool pads_unread = listed && (q_folded || l.fan == 1 || presum);
+  if (wf) TRY(launch_attn_bwd_wf(a, reinterpret_cast<const uint32_t*>(ws + l.amask), pads_unread, st));
+  else if (w1) TRY(launch_attn_bwd_w1(a, pads_unread, st));
+  else TRY(form == ATTN_SQ1 ? launch_attn_bwd_sq1(a, st) : launch_attn_bwd(a, st));
+  // weight gradients of Wo, Wk, Wv, Wq: one fork right behind the attention backward, off the dX chain
+  GemmProblem wg3[3];
+  wg3[0] = gp_wgrad(ws + w.dkv, a.lddkv, xn, d, Lg.wk, d, d, ns);
+  wg3[1] = gp_wgrad(ws + w.dkv + d, a.lddkv, xn, d, Lg.wv, d, d, ns);
+  if (qall) wg3[2] = gp_wgrad(ws + w.dkv + 2 * d, a.lddkv, xn, d, Lg.wq, d, d, ns);
+  else wg3[2] = gp_wgrad(ws + w.dq, d, xn + (size_t)w.qpos * d, S * d, Lg.wq, d, d, l.n_in);
+  // first layer, one query row per sequence: dQ.Wq is a [n_in, d] product whose rows join the big dX GEMM below
+  // through its fan-in epilogue — computed here, before the weight gradients start competing for the CUs
+  // (as a trailing accumulate-GEMM it took 26 us on the critical path under them)
+  const bool q_via_res = !qall && i == 0;
+  float* dxq = ws + w.dctx;                      // free again: the attention backward has consumed it
+  if (q_via_res && !q_folded) {
+    GemmProblem xq = gp(ws + w.dq, d, 0, Lp.wq, d, 1, dxq, d, l.n_in, d, d);
+    xq.no_deep = 1;   // runs beside the side stream's weight gradients (at C5 the deep form waited 110 us for whole CUs)
+    TRY(run1(xq, st));
+  }
+  // fork 2: they need the attention backward's dK / dV / dQ.  With the fused backward the side stream already
+  // holds W2 / W1 / Wo (~90 us, the step's tail): the K/V/Q weight gradients then follow the dX GEMM on the MAIN
+  // stream instead — one event less, and the side stream ends before the scatter does.
+  // (round 2: W2 / W1 / Wo are ONE launch of ~45 us now, the side stream is free again when the attention backward
+  // ends: the K / V / Q weight gradients go back to it, 0.3151 -> 0.3124 ms/step; PS_WG3_SIDE=0: main stream)
+  // (later in round 2: with forks signalled by the next kernel the main stream lost its two bubbles and ENDED 30 us before
+  // the side stream — score scatter 28 + W2/W1/Wo 45 + these 16 us; back on the main stream: 0.2861 -> 0.2801 ms/step)
+  const bool wg3_main = fused && pb.wg3_main;
+  const int32_t* vr = reinterpret_cast<const int32_t*>(ws + w.vrows);
+  const int32_t* vc = reinterpret_cast<const int32_t*>(ws + w.vcount);
+  if (listed) {
+    wg3[0].ridx = vr; wg3[0].rcount = vc;
+    wg3[1].ridx = vr; wg3[1].rcount = vc;
+  }
+  if (!wg3_main) {
+    TRY(side_fork(st));
+    TRY(side_run(wg3, 3, st));
+  }
+  if (pb.wgrad_early && !fused) {
+    GemmProblem wgo[1] = {c.wgrad_wo(i)};
+    TRY(side_run(wgo, 1, st));
+  }
+  // d xn = dK.Wk + dV.Wv (+ dQ.Wq)
+  float* dxn = i == 0 ? ws + w.dx : ws + w.dxn;
+  GemmProblem x = gp(ws + w.dkv, a.lddkv, 0, Lp.wk, d, 1, dxn, d, ns, d, qall ? 3 * d : 2 * d);
+  x.kseg = d; x.Bseg[1] = Lp.wv; x.Bseg[2] = Lp.wq;
+  if (i == 0) {   // + residual path of `out = dropout(context) + inputs`, summed over the replicas
+    x.res.mode = RES_FANIN; x.res.ptr = ws + w.dy1; x.res.ld = d; x.res.Sq = l.Sq; x.res.fan = l.fan;
+    x.res.S = S; x.res.qpos = w.qpos; res_finish(x.res);
+    if (q_folded) {   // both partial rows already hold the replicas' fan-in sum: nothing left to walk here
+      x.res.extra = ws + w.dln1; x.res.extra2 = (w1 && !(wf && attn_bwd_wf_two_partials(a))) ? nullptr : ws + w.dln1 + (size_t)l.n_in * d; x.res.extra_ld = d; x.res.ptr = nullptr;
+    }
+    else if (q_via_res) { x.res.extra = dxq; x.res.extra_ld = d; }
+    if (presum) {   // fan-in summed up front: one row per sequence beside the dQ.Wq row, nothing to walk
+      float* fsum = ws + w.dln1;          // (free: the FF LayerNorm backward has consumed d ln1)
+      TRY(launch_fanin_sum(ws + w.dy1, d, l.n_in, l.fan, d, fsum, st));
+      x.res.ptr = nullptr; x.res.extra = dxq; x.res.extra2 = fsum; x.res.extra_ld = d;
+    }
+  }
+  // (the dX product over the row list only when its fan-in residual is already folded: walking 21 replica rows per
+  // query row in a third of the workgroups made it slower than the dense form — 144 vs 106 us at C5)
+  if (pads_unread) { x.ridx = vr; x.rcount = vc; }
+  if (!dx_fused) TRY(run1(x, st));
+  if (wg3_main) {
+    if (pb.wg3_last && c.in.caller_flushes_tail) { for (int q = 0; q < 3; ++q) c.out.wg3_last[q] = wg3[q]; c.out.wg3_last_n = 3; }
+    else TRY(run_wgrads(wg3, 3, st));
+  }
+  if (!qall && !q_via_res) {
+    GemmProblem xq = gp(ws + w.dq, d, 0, Lp.wq, d, 1, dxn + (size_t)w.qpos * d, S * d, l.n_in, d, d);
+    xq.accumulate = 1;
+    TRY(run1(xq, st));
+  }
+  return PS_OK;
+}
+
+int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui,
+                        const float* valid, float* ws, const Ws& w, hipStream_t st, const EncBwdIn& in, EncBwdOut& out) {
+  const int B = D.B, d = D.d, S = w.S, NL = D.n_layers;
+  PS_REQUIRE(G.final_ln_g && G.final_ln_b, "backward: null final LayerNorm gradient");
+  const EncPlan pl = enc_plan(D, P, ws, w, in.rows_listed, valid);
+  out = EncBwdOut();
+  const EncBwd c = {D, P, G, ws, w, st, pl, in, out};
+  const bool fuse_last = pl.bwd.fuse_last;
   side_set_light((int64_t)B * S * d <= ((int64_t)2 << 20));   // C2: 1.03 M elements of x; review transformer 10 M; C5 5.5 M
-  static const bool bwd_fuse_on = ps_env_int("PS_NO_FUSE_BWD", 0) == 0;
-  const int bwd_fuse_min = fuse_bwd_min_slot();
-  g_item_scatter_taken = 0;
-  const bool fuse_last = NL > 0 && fold && bwd_fuse_on && ps_fusion_enabled() && w.layer[NL - 1].Sq == 1 &&
-                         mlp_fused_serves(d, F) && w.wsplit && w.layer[NL - 1].M2 == w.Mf && w.Mf >= bwd_fuse_min &&
-                         mlp_bwd_fused_blocks(w.Mf) <= w.lnrows && fold->n + 3 <= PS_MAX_COLFOLD;
-  if (score_on_side && !(fuse_last && w.R > 1)) {
+  const ScoreArgs* score_fused = fuse_last && w.R > 1 ? in.score_on_side : nullptr;
+  if (in.score_on_side && !score_fused) {
     // not the fused form: d enc is needed first, so the score backward is cut in two — its d enc half leads the main
     // stream, its table scatter (the expensive half: 127 us of scattered atomics at C5) goes to the side stream
-    ScoreArgs t = *score_on_side;
+    ScoreArgs t = *in.score_on_side;
     t.denc = ws + w.denc;
     SideCtx* sc = side_ctx_on(st);
     if (sc && w.R > 1) {
@@ -1203,22 +1420,23 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
     } else {
       TRY(launch_score_bwd(t, st));
     }
-    score_on_side = nullptr;
   }
-  if (fuse_last) {
-    // nothing here: launched inside the layer loop below
-  } else if (NL > 0) {
-    const LayerWs& l = w.layer[NL - 1];
-    f.x = ws + l.y2; f.ldx = d; f.rows = w.Mf; f.dx = ws + w.dy2; f.lddx = d;
-    f.colsum = G.layer[NL - 1].b2;
-    if (drop) { f.out2 = ws + w.do2; f.drop2 = make_drop(D, PS_SITE_FF2(NL - 1)); }
-    park_colsums(f, ws, w, fold);
-    TRY(launch_ln_bwd(f, st));
-  } else {
-    PS_CHECK_HIP(hipMemsetAsync(ws + w.dx, 0, sizeof(float) * (size_t)B * S * d, st));
-    f.x = ws + w.x + (size_t)w.qpos * d; f.ldx = S * d; f.rows = B;
-    f.dx = ws + w.dx + (size_t)w.qpos * d; f.lddx = S * d;
-    park_colsums(f, ws, w, fold);
+  if (!fuse_last) {   // 2. final LayerNorm backward (fused form: inside the last layer's kernel)
+    LnBwdArgs f;
+    memset(&f, 0, sizeof(f));
+    f.dy = ws + w.denc; f.lddy = d; f.stats = ws + w.fin_stats; f.g = P.final_ln_g; f.d = d;
+    f.dgamma = G.final_ln_g; f.dbeta = G.final_ln_b;
+    if (NL > 0) {
+      const LayerWs& l = w.layer[NL - 1];
+      f.x = ws + l.y2; f.ldx = d; f.rows = w.Mf; f.dx = ws + w.dy2; f.lddx = d;
+      f.colsum = G.layer[NL - 1].b2;
+      if (c.drop()) { f.out2 = ws + w.do2; f.drop2 = make_drop(D, PS_SITE_FF2(NL - 1)); }
+    } else {
+      PS_CHECK_HIP(hipMemsetAsync(ws + w.dx, 0, sizeof(float) * (size_t)B * S * d, st));
+      f.x = ws + w.x + (size_t)w.qpos * d; f.ldx = S * d; f.rows = B;
+      f.dx = ws + w.dx + (size_t)w.qpos * d; f.lddx = S * d;
+    }
+    park_colsums(f, ws, w, in.fold);
     TRY(launch_ln_bwd(f, st));
   }
   // 3. layers, last to first
@@ -1228,276 +1446,23 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
     const PsLayerTensors& Lg = G.layer[i];
     PS_REQUIRE(Lg.wk && Lg.wv && Lg.wq && Lg.wo && Lg.w1 && Lg.w2 && Lg.bk && Lg.bv && Lg.bq && Lg.bo && Lg.b1 &&
                Lg.b2 && Lg.ff_ln_g && Lg.ff_ln_b, "backward: layer %d has null gradients", i);
-    const float* xin = i == 0 ? ws + w.x : ws + w.layer[i - 1].y2;
-    const float* xn = ws + l.xn;
-    const int ns = l.n_in * S, M2 = l.M2;
-    const float* do2 = drop ? ws + w.do2 : ws + w.dy2;
     const bool fused = fuse_last && i == NL - 1;
-    static const bool wgrad_early = ps_diag_int("PS_WGRAD_LATE", 0) == 0;
-    if (fused) {
-      MlpBwdArgs m;
-      memset(&m, 0, sizeof(m));
-      m.M = M2; m.F = F;
-      m.denc = ws + w.denc; m.y2 = ws + l.y2; m.stf = ws + w.fin_stats; m.gf = P.final_ln_g;
-      m.y1 = ws + l.y1; m.st1 = ws + l.ff_stats; m.g1 = Lp.ff_ln_g; m.a1 = ws + l.a1;
-      m.wo = Lp.wo; m.w1 = Lp.w1; m.w2 = Lp.w2;
-      m.drop_ctx = make_drop(D, PS_SITE_CTX(i)); m.drop_ff1 = make_drop(D, PS_SITE_FF1(i));
-      m.drop_ff2 = make_drop(D, PS_SITE_FF2(i));
-      if (score_on_side) {   // d enc from the scores (see MlpBwdArgs::item_scores)
-        const ScoreArgs& sa = *score_on_side;
-        m.item_scores = sa.item_scores; m.target = sa.target; m.neg_items = sa.neg_items; m.product_emb = sa.product_emb;
-        m.B = sa.B; m.K = sa.K; m.pos_weight = sa.pos_weight; m.P = sa.P; m.scale = sa.scale; m.scale_dev = sa.scale_dev;
-        if (item_scatter_fused_slot() != 0 && !ps_deterministic() && g_wg3_defer_ok && sa.part == 0 && sa.enc && sa.g_product_emb) {
-          m.enc = sa.enc; m.g_product_emb = sa.g_product_emb;
-          m.g_product_bias = sa.bias_product ? sa.g_product_bias : nullptr;
-        }
-      }
-      m.x3 = make_wsplit(D, P, ws, w);                 // the fragment streams the forward's embed launch left in the workspace
-      m.do2 = const_cast<float*>(do2); m.da1 = ws + w.da1; m.dy1 = ws + w.dy1;
-      m.dout = drop ? ws + w.do_ : ws + w.dy1; m.dctx = ws + w.dctx;
-      const int nwg = mlp_bwd_fused_blocks(M2);
-      {   // parked column sums: {final LN gamma, beta, b2}, {b1}, {FF LN gamma, beta, bo}
-        ColFold& c0 = fold->e[fold->n];
-        m.part_f = ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * d;
-        c0.partial = m.part_f; c0.nblk = nwg; c0.d = d;
-        c0.dst[0] = G.final_ln_g; c0.dst[1] = G.final_ln_b; c0.dst[2] = Lg.b2;
-        ++fold->n;
-        ColFold& c1 = fold->e[fold->n];
-        m.part_1 = ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * d;
-        c1.partial = m.part_1; c1.nblk = nwg; c1.d = d;
-        c1.dst[0] = Lg.ff_ln_g; c1.dst[1] = Lg.ff_ln_b; c1.dst[2] = Lg.bo;
-        ++fold->n;
-        ColFold& c2 = fold->e[fold->n];
-        m.part_b1 = ws + w.gcpart;
-        c2.partial = m.part_b1; c2.nblk = mlp_bwd_b1_rows(M2, F); c2.d = F;
-        c2.dst[0] = Lg.b1; c2.dst[1] = nullptr; c2.dst[2] = nullptr;
-        ++fold->n;
-      }
-      // (measured and dropped: the table scatter of the score backward — it needs nothing of this backward — started beside
-      // the fused kernel below, its fork carried by that kernel: starved by 252 workgroups that own their CUs' LDS it took
-      // 74 us instead of 29 and slowed the attention backward behind it, 0.278 -> 0.282 ms/step)
-      TRY(launch_mlp_bwd_fused(m, st));
-      GemmProblem wg[1] = {gp_wgrad(do2, d, ws + l.h1, F, Lg.w2, d, F, M2)};
-      GemmProblem wg1[1] = {gp_wgrad(ws + w.da1, F, ws + l.ln1, d, Lg.w1, F, d, M2)};
-      GemmProblem wgo[1] = {gp_wgrad(m.dout, d, ws + l.ctx, d, Lg.wo, d, d, M2)};
-      TRY(side_fork(st));                           // fork 1: W2, W1, Wo weight gradients under the attention backward
-      if (score_on_side && m.g_product_emb) {
-        // the fused kernel above has added the item rows: what is left of the score backward are its word tasks (2 B workgroups,
-        // 14 us alone at C2).  Leading the side stream, as the whole scatter does below, they only moved the W2 / W1 / Wo group
-        // into the attention backward and the embedding scatter (42 -> 52-58 us, the side stream still the last to end: a wash);
-        // the caller launches them as the main stream's LAST kernel instead, behind its K / V / Q weight gradients — the main
-        // stream ended 12 us before the side stream, which now carries the group alone, and the join's value is there when the
-        // main stream arrives (C2 0.2133 -> 0.2067 ms/step, profiles/item_scatter_fused_notes.md)
-        g_score_words_last = true;
-        g_item_scatter_taken = 1;
-      } else if (score_on_side) {                   // ... led by the table scatter of the score backward (behind them instead: 0.284 -> 0.293 ms/step)
-        ScoreArgs t = *score_on_side;
-        t.denc = nullptr;
-        SideCtx* sc = side_ctx_on(st);
-        TRY(launch_score_bwd(t, sc ? sc->stream : st));
-      }
-      // (a second side stream for W1 / Wo beside W2 measured 0.389 vs 0.368 ms: slower)
-      // one launch for the three (the flat group form: every member keeps its own split count; three launches of ~250
-      // latency-bound workgroups one after the other took 86 us at C2; review transformer 0.563 -> 0.543 ms/step, C2 0.3156 ->
-      // 0.3144).  PS_WGRAD_GROUP_ROWS=0 restores the separate launches.
-      static const int wg_group_rows = ps_diag_int("PS_WGRAD_GROUP_ROWS", (1 << 30));
-      if (M2 <= wg_group_rows) {
-        GemmProblem all3[3] = {wg[0], wg1[0], wgo[0]};
-        TRY(side_run(all3, 3, st));
-      } else {
-        TRY(side_run(wg, 1, st));
-        TRY(side_run(wg1, 1, st));
-        TRY(side_run(wgo, 1, st));
-      }
-    } else {
-    // FFN backward
-      GemmProblem p = gp(do2, d, 0, Lp.w2, F, 1, ws + w.da1, F, M2, F, d);      // d h1 = do2 . W2
-      p.act = ACT_GELU_BWD; p.act_aux = ws + l.a1; p.drop = make_drop(D, PS_SITE_FF1(i)); p.colsum = Lg.b1;
-      if (fold && fold->n < PS_MAX_COLFOLD && i == NL - 1) {      // park the b1 column sums (one buffer: last layer only)
-        ColFold& cf = fold->e[fold->n++];
-        p.colsum_part = ws + w.gcpart;
-        cf.partial = p.colsum_part; cf.nblk = 4 * ps_cdiv(M2, 64); cf.d = F;
-        cf.dst[0] = Lg.b1; cf.dst[1] = nullptr; cf.dst[2] = nullptr;
-      }
-      TRY(run1(p, st));
-      // dW2 += do2^T . h1 and dW1 += da1^T . ln1 are launched further down, once the dX chain of the MLP is through
-      // (beside it they slowed every link: 44 vs 33 us for the GEMM below); they then share the machine with the
-      // attention backward and the big dX GEMM instead.  Measured a wash in step time (both orders 0.509 ms): the
-      // backward is throughput-bound once both streams are busy.
-      GemmProblem wg[1] = {gp_wgrad(do2, d, ws + l.h1, F, Lg.w2, d, F, M2)};
-      GemmProblem wg1[1] = {gp_wgrad(ws + w.da1, F, ws + l.ln1, d, Lg.w1, F, d, M2)};
-      GemmProblem q = gp(ws + w.da1, F, 0, Lp.w1, d, 1, ws + w.dln1, d, M2, d, F);  // d ln1 = da1 . W1
-      TRY(run1(q, st));
-      // fork 1: the two big weight gradients (W2, W1) start as soon as d a1 exists, under the LN backward, the Wo dX
-      // GEMM and the attention backward.  (Forked one GEMM later, behind d ctx, the side stream's 112 us of weight
-      // gradients ended 13 us after the main chain and the step paid a late join on top.)
-      if (wgrad_early) {
-        TRY(side_fork(st));
-        TRY(side_run(wg, 1, st));
-        TRY(side_run(wg1, 1, st));
-      }
-      LnBwdArgs n;
-      memset(&n, 0, sizeof(n));
-      n.dy = ws + w.dln1; n.lddy = d; n.x = ws + l.y1; n.ldx = d; n.stats = ws + l.ff_stats; n.g = Lp.ff_ln_g;
-      n.rows = M2; n.d = d;
-      n.res.mode = RES_DIRECT; n.res.ptr = ws + w.dy2; n.res.ld = d;            // residual  output + x
-      n.dx = ws + w.dy1; n.lddx = d;
-      if (drop) { n.out2 = ws + w.do_; n.drop2 = make_drop(D, PS_SITE_CTX(i)); }
-      n.colsum = Lg.bo; n.dgamma = Lg.ff_ln_g; n.dbeta = Lg.ff_ln_b;
-      park_colsums(n, ws, w, fold);
-      TRY(launch_ln_bwd(n, st));
-      const float* dout0 = drop ? ws + w.do_ : ws + w.dy1;
-      GemmProblem pc = gp(dout0, d, 0, Lp.wo, d, 1, ws + w.dctx, d, M2, d, d);    // d ctx = do . Wo
-      TRY(run1(pc, st));
-      if (!wgrad_early) {
-        GemmProblem wgo0[1] = {gp_wgrad(dout0, d, ws + l.ctx, d, Lg.wo, d, d, M2)};
-        TRY(side_fork(st));                         // fork 1 (late form): W2, W1, Wo weight gradients under the attention backward
-        TRY(side_run(wg, 1, st));
-        TRY(side_run(wg1, 1, st));
-        TRY(side_run(wgo0, 1, st));
-      }
-    }
-
-    const float* dout = drop ? ws + w.do_ : ws + w.dy1;
-    // attention backward
-    {
-      GemmProblem wgo[1] = {gp_wgrad(dout, d, ws + l.ctx, d, Lg.wo, d, d, M2)};
-      AttnArgs a;
-      memset(&a, 0, sizeof(a));
-      a.n_in = l.n_in; a.fan = l.fan; a.H = D.H; a.S = S; a.Sq = l.Sq; a.d = d; a.dh = d / D.H; a.qpos = w.qpos;
-      a.seq_div = l.n_in / B; a.L = D.L; a.P = D.product_size; a.ui = ui; a.valid = valid;
-      a.kp = ws + l.kp; a.vp = ws + l.vp; a.qp = ws + l.qp; a.attn = ws + l.attn;
-      a.drop = make_drop(D, PS_SITE_ATTN(i));
-      a.dctx = ws + w.dctx;
-      const bool qall = l.Sq == S;
-      a.lddkv = qall ? 3 * d : 2 * d;
-      a.dkv = ws + w.dkv;
-      a.dq = qall ? ws + w.dkv + 2 * d : ws + w.dq;
-      a.lddq = qall ? 3 * d : d;
-      a.dbq = Lg.bq; a.dbk = Lg.bk; a.dbv = Lg.bv;
-      a.qscale = 1.f / sqrtf((float)(d / D.H));
-      attn_finish(a);
-      const bool sq1 = attn_sq1_fits(a);
-      if (sq1 && fold && fold->n < PS_MAX_COLFOLD) {
-        // bias gradients: one parked row per sequence instead of n_in same-address atomics per column
-        ColFold& cf = fold->e[fold->n++];
-        a.bias_part = ws + w.abpart + (size_t)i * w.layer[D.n_layers - 1].n_in * 3 * d;
-        cf.partial = a.bias_part; cf.nblk = l.n_in; cf.d = d;
-        cf.dst[0] = Lg.bq; cf.dst[1] = Lg.bk; cf.dst[2] = Lg.bv;
-      }
-      // first layer, one query row per sequence, d == 128: dQ.Wq rides in the attention backward's tail (two partial
-      // rows per sequence in the free d ln1 buffer) instead of a [n_in,128]x[128,128] GEMM launch of its own
-      const bool wf = sq1 && a.fan > 1 && attn_wf_fits(a);   // one wave per (sequence, four heads), replicas inside
-      const bool w1 = wf || (sq1 && attn_w1_fits(a));       // one wave per sequence (no replicas)
-      const bool q_folded = sq1 && !qall && i == 0 && ps_fusion_enabled() &&
-                            (w1 ? (!wf || d == 128) && (size_t)(wf ? 2 : 1) * l.n_in <= (size_t)M2
-                                : d == 128 && attn_sq1_split(a) == 2 && (size_t)2 * l.n_in <= (size_t)M2);
-      if (q_folded) { a.wq = Lp.wq; a.dxq_part = ws + w.dln1; a.fanin_src = ws + w.dy1; }
-      // ... and, one-layer encoder with replicas: so does the K / V input gradient itself (AttnArgs::kvb_stream) — no dX GEMM launch
-      // on the dependent chain; the embed scatter adds the two head groups' partial rows (EmbedBwdArgs::dx2)
-      static const bool rows_on0 = ps_env_int("PS_NO_ROWLIST", 0) == 0;
-      static const bool dx_fused_on = ps_env_int("PS_KVDX_FUSED", 1) != 0;
-      const WSplit kvs = (i == 0 && NL == 1) ? make_wsplit(D, P, ws, w) : WSplit{};
-      // (FS query encoder only: its fused backward reads d query_emb as the two partials; the AVG branch copies one row of dx)
-      const bool dx_fused = dx_fused_on && wf && q_folded && i == 0 && NL == 1 && d == 128 && kvs.on && kvs.bwd_kv && !ps_deterministic() &&
-                            rows_on0 && rows_listed && !qall && w.qpos == 0 && w.vrows != 0 && l.n_in == B && attn_bwd_wf_two_partials(a) &&
-                            D.query_encoder == PS_QENC_FS;
-      if (dx_fused) { a.kvb_stream = kvs.bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; }
-      g_dx_two_partials = dx_fused;
-      // valid rows only (below): the dK / dV rows of padded positions are then never read, and never written
-      const bool listed0 = rows_on0 && rows_listed && sq1 && i == 0 && NL == 1 && !qall && w.qpos == 0 && w.vrows != 0 && l.n_in == B;
-      // round 4: where dQ.Wq is NOT folded (d != 128: the C5 shard) the replicas' fan-in is summed by a launch of its own
-      // (launch_fanin_sum, below) so that the dX product can still run over the row list: 133 -> ~50 us at C5
-      const bool presum = listed0 && !q_folded && l.fan > 1 && l.Sq == 1 && !qall && i == 0 && (d % 4) == 0;
-      if (wf) TRY(launch_attn_bwd_wf(a, reinterpret_cast<const uint32_t*>(ws + l.amask), listed0 && (q_folded || l.fan == 1 || presum), st));
-      else if (w1) TRY(launch_attn_bwd_w1(a, listed0 && (q_folded || l.fan == 1 || presum), st));
-      else TRY(sq1 ? launch_attn_bwd_sq1(a, st) : launch_attn_bwd(a, st));
-      // weight gradients of Wo, Wk, Wv, Wq: one fork right behind the attention backward, off the dX chain
-      GemmProblem wg3[3];
-      wg3[0] = gp_wgrad(ws + w.dkv, a.lddkv, xn, d, Lg.wk, d, d, ns);
-      wg3[1] = gp_wgrad(ws + w.dkv + d, a.lddkv, xn, d, Lg.wv, d, d, ns);
-      if (qall) wg3[2] = gp_wgrad(ws + w.dkv + 2 * d, a.lddkv, xn, d, Lg.wq, d, d, ns);
-      else wg3[2] = gp_wgrad(ws + w.dq, d, xn + (size_t)w.qpos * d, S * d, Lg.wq, d, d, l.n_in);
-      // first layer, one query row per sequence: dQ.Wq is a [n_in, d] product whose rows join the big dX GEMM below
-      // through its fan-in epilogue — computed here, before the weight gradients start competing for the CUs
-      // (as a trailing accumulate-GEMM it took 26 us on the critical path under them)
-      const bool q_via_res = !qall && i == 0;
-      float* dxq = ws + w.dctx;                      // free again: the attention backward has consumed it
-      if (q_via_res && !q_folded) {
-        GemmProblem xq = gp(ws + w.dq, d, 0, Lp.wq, d, 1, dxq, d, l.n_in, d, d);
-        xq.no_deep = 1;   // runs beside the side stream's weight gradients (at C5 the deep form waited 110 us for whole CUs)
-        TRY(run1(xq, st));
-      }
-      // fork 2: they need the attention backward's dK / dV / dQ.  With the fused backward the side stream already
-      // holds W2 / W1 / Wo (~90 us, the step's tail): the K/V/Q weight gradients then follow the dX GEMM on the MAIN
-      // stream instead — one event less, and the side stream ends before the scatter does.
-      // (round 2: W2 / W1 / Wo are ONE launch of ~45 us now, the side stream is free again when the attention backward
-      // ends: the K / V / Q weight gradients go back to it, 0.3151 -> 0.3124 ms/step; PS_WG3_SIDE=0: main stream)
-      // (later in round 2: with forks signalled by the next kernel the main stream lost its two bubbles and ENDED 30 us before
-      // the side stream — score scatter 28 + W2/W1/Wo 45 + these 16 us; back on the main stream: 0.2861 -> 0.2801 ms/step)
-      static const int wg3_side = ps_diag_int("PS_WG3_SIDE", -1);
-      static const bool wg3_main_on = wg3_side >= 0 ? wg3_side == 0 : fork_by_kernel();
-      const bool wg3_main = fused && wg3_main_on && ns <= 2 * M2;   // (review transformer: 78k K/V rows vs 1.5k replica rows -> side)
-      // valid rows only: padded positions have exactly-zero dK / dV rows (their attention weights are 0), so the K/V
-      // weight gradients (and the dX product below) run over the batch's row list instead of all n_in*S rows
-      static const bool rows_on = ps_env_int("PS_NO_ROWLIST", 0) == 0;
-      const bool listed = rows_on && rows_listed && sq1 && i == 0 && NL == 1 && !qall && w.qpos == 0 && w.vrows != 0 && l.n_in == B;
-      const int32_t* vr = reinterpret_cast<const int32_t*>(ws + w.vrows);
-      const int32_t* vc = reinterpret_cast<const int32_t*>(ws + w.vcount);
-      if (listed) {
-        wg3[0].ridx = vr; wg3[0].rcount = vc;
-        wg3[1].ridx = vr; wg3[1].rcount = vc;
-      }
-      if (!wg3_main) {
-        TRY(side_fork(st));
-        TRY(side_run(wg3, 3, st));
-      }
-      if (wgrad_early && !fused) TRY(side_run(wgo, 1, st));
-      // d xn = dK.Wk + dV.Wv (+ dQ.Wq)
-      float* dxn = i == 0 ? ws + w.dx : ws + w.dxn;
-      GemmProblem x = gp(ws + w.dkv, a.lddkv, 0, Lp.wk, d, 1, dxn, d, ns, d, qall ? 3 * d : 2 * d);
-      x.kseg = d; x.Bseg[1] = Lp.wv; x.Bseg[2] = Lp.wq;
-      if (i == 0) {   // + residual path of `out = dropout(context) + inputs`, summed over the replicas
-        x.res.mode = RES_FANIN; x.res.ptr = ws + w.dy1; x.res.ld = d; x.res.Sq = l.Sq; x.res.fan = l.fan;
-        x.res.S = S; x.res.qpos = w.qpos; res_finish(x.res);
-        if (q_folded) {   // both partial rows already hold the replicas' fan-in sum: nothing left to walk here
-          x.res.extra = ws + w.dln1; x.res.extra2 = (w1 && !(wf && attn_bwd_wf_two_partials(a))) ? nullptr : ws + w.dln1 + (size_t)l.n_in * d; x.res.extra_ld = d; x.res.ptr = nullptr;
-        }
-        else if (q_via_res) { x.res.extra = dxq; x.res.extra_ld = d; }
-        if (presum && listed && q_via_res) {   // fan-in summed up front: one row per sequence beside the dQ.Wq row, nothing to walk
-          float* fsum = ws + w.dln1;          // (free: the FF LayerNorm backward has consumed d ln1)
-          TRY(launch_fanin_sum(ws + w.dy1, d, l.n_in, l.fan, d, fsum, st));
-          x.res.ptr = nullptr; x.res.extra = dxq; x.res.extra2 = fsum; x.res.extra_ld = d;
-        }
-      }
-      // (the dX product over the row list only when its fan-in residual is already folded: walking 21 replica rows per
-      // query row in a third of the workgroups made it slower than the dense form — 144 vs 106 us at C5)
-      if (listed && (q_folded || l.fan == 1 || (presum && q_via_res))) { x.ridx = vr; x.rcount = vc; }
-      if (!dx_fused) TRY(run1(x, st));
-      if (wg3_main) {
-        static const bool wg3_last = ps_diag_int("PS_WG3_LAST", 1) != 0;
-        if (wg3_last && g_wg3_defer_ok && i == 0) { for (int q = 0; q < 3; ++q) g_wg3_last[q] = wg3[q]; g_wg3_last_n = 3; }
-        else TRY(run_wgrads(wg3, 3, st));
-      }
-      if (!qall && !q_via_res) {
-        GemmProblem xq = gp(ws + w.dq, d, 0, Lp.wq, d, 1, dxn + (size_t)w.qpos * d, S * d, l.n_in, d, d);
-        xq.accumulate = 1;
-        TRY(run1(xq, st));
-      }
-    }
+    if (fused) TRY(bwd_fused_last(c, score_fused));
+    else TRY(bwd_ffn(c, i));
+    TRY(bwd_attention(c, i, fused, ui, valid));
     if (i != 0) {   // pre-LayerNorm backward -> grad wrt the previous layer's output
       TRY(side_join(st));   // the next layer reuses the scratch buffers the side-stream GEMMs read
       PS_REQUIRE(Lg.ln_g && Lg.ln_b, "backward: layer %d null pre-LN gradient", i);
       LnBwdArgs n;
       memset(&n, 0, sizeof(n));
-      n.dy = ws + w.dxn; n.lddy = d; n.x = xin; n.ldx = d; n.stats = ws + l.pre_stats; n.g = Lp.ln_g;
-      n.rows = ns; n.d = d;
+      n.dy = ws + w.dxn; n.lddy = d; n.x = ws + w.layer[i - 1].y2; n.ldx = d; n.stats = ws + l.pre_stats; n.g = Lp.ln_g;
+      n.rows = l.n_in * S; n.d = d;
       n.res.mode = RES_FANIN; n.res.ptr = ws + w.dy1; n.res.ld = d; n.res.Sq = l.Sq; n.res.fan = l.fan;
       n.res.S = S; n.res.qpos = w.qpos; res_finish(n.res);
       n.dx = ws + w.dy2; n.lddx = d;
-      if (drop) { n.out2 = ws + w.do2; n.drop2 = make_drop(D, PS_SITE_FF2(i - 1)); }
+      if (c.drop()) { n.out2 = ws + w.do2; n.drop2 = make_drop(D, PS_SITE_FF2(i - 1)); }
       n.colsum = G.layer[i - 1].b2; n.dgamma = Lg.ln_g; n.dbeta = Lg.ln_b;
-      park_colsums(n, ws, w, fold);
+      park_colsums(n, ws, w, in.fold);
       TRY(launch_ln_bwd(n, st));
     }
   }
@@ -1507,19 +1472,7 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
 // --------------------------------------------------------------------- backward
 static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                              float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
-                             ps_stream_t stream);
-extern "C" int ps_tem_backward(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
-                               float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
-                               ps_stream_t stream) {
-  const int rc = tem_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream);
-  if (rc != PS_OK) { side_abort(); enc_clear_call_flags(); }    // never leave the side stream waiting behind a failed call
-  return rc;
-}
-static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
-                             float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
-                             ps_stream_t stream) {
-  enc_clear_call_flags();
-  g_item_scatter_taken = 0;
+                             ps_stream_t stream, EncBwdOut& out) {
   PS_REQUIRE(desc && params && batch && ws && grads, "backward: null argument");
   PsTemDesc D = *desc;
   D.C = 0;
@@ -1529,8 +1482,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   const PsTemTensors& P = *params;
   const PsTemTensors& G = *grads;
   const bool tem = D.model == PS_MODEL_TEM;
-  const bool drop = D.training && D.dropout > 0.f;
-  const int B = D.B, d = D.d, S = w.S, NL = tem ? D.n_layers : 0, F = D.F;
+  const int B = D.B, d = D.d, S = w.S, NL = tem ? D.n_layers : 0;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
   float* ghist = D.sep_prod_emb ? G.hist_product_emb : G.product_emb;
   // G.word_emb null: the word table is frozen (a pretrained table, nn.Embedding.from_pretrained): no kernel reads or writes a
@@ -1555,17 +1507,13 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the dX products read the TRANSPOSED weight planes (gemm.hip)
   ColFoldList fold;
   fold.n = 0;
-  bool score_words_last = false;    // enc_layers_backward left the score backward's word tasks to this function (its last launch)
   const float* dqe = ws + w.denc;   // grad wrt query_emb rows (QEM: enc IS query_emb)
   int lddqe = d;
   if (tem) {
-    g_wg3_defer_ok = true; g_wg3_last_n = 0; g_score_words_last = false;
-    const int rc_enc = enc_layers_backward(D, P, G, batch->u_item_idxs, nullptr, ws, w, st, &fold, score_deferred ? &s : nullptr,
-                                           rows_list_ok(D));
-    g_wg3_defer_ok = false;
-    score_words_last = g_score_words_last;
-    g_score_words_last = false;
-    if (rc_enc != PS_OK) { g_wg3_last_n = 0; return rc_enc; }
+    EncBwdIn in;
+    in.fold = &fold; in.score_on_side = score_deferred ? &s : nullptr; in.rows_listed = rows_list_ok(D);
+    in.caller_flushes_tail = true;     // out.wg3_last and out.score_words_last: this function's last launches
+    TRY(enc_layers_backward(D, P, G, batch->u_item_idxs, nullptr, ws, w, st, in, out));
     dqe = ws + w.dx;      // row 0 of each sequence is the query embedding
     lddqe = S * d;
   } else if (ps_model_attn(D.model)) {
@@ -1579,7 +1527,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   memset(&e, 0, sizeof(e));
   e.B = B; e.Q = D.Q; e.L = D.L; e.S = S; e.d = d; e.P = D.product_size; e.V = D.vocab_size; e.tem = tem;
   e.qw = batch->query_word_idxs; e.ui = batch->u_item_idxs; e.dx = ws + w.dx;
-  if (enc_take_dx_two_partials()) e.dx2 = ws + w.dxn;   // the attention backward left d x as two partial rows per position
+  if (out.dx_two_partials) e.dx2 = ws + w.dxn;   // the attention backward left d x as two partial rows per position
   e.drop_fs = make_drop(D, PS_SITE_FS);
   e.g_hist_tab = ghist; e.g_word_emb = G.word_emb;
   if (D.query_encoder == PS_QENC_FS) {
@@ -1612,20 +1560,29 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
     e.dqmean_d = ws + w.dqmean;
   }
   e.fold = fold;
-  const int rc_sc = launch_embed_scatter(e, st);
-  if (rc_sc != PS_OK) { g_wg3_last_n = 0; return rc_sc; }
+  TRY(launch_embed_scatter(e, st));
   if (fw_by_gemm) {      // g_fs_w[o][i] += sum_b dqpre[b][o] * qmean[b][i]  (text_encoder.py:38)
-    PS_REQUIRE(g_wg3_last_n <= 3, "backward: deferred weight-gradient group is full");
-    g_wg3_last[g_wg3_last_n++] = gp_wgrad(ws + w.dqpre, d, ws + w.qmean, d, G.fs_w, d, d, B);
+    PS_REQUIRE(out.wg3_last_n <= 3, "backward: deferred weight-gradient group is full");
+    out.wg3_last[out.wg3_last_n++] = gp_wgrad(ws + w.dqpre, d, ws + w.qmean, d, G.fs_w, d, d, B);
   }
-  TRY(flush_wg3_last(st));
-  if (score_words_last) {      // the word tasks of the score backward (the fused backward has scattered the item rows)
+  if (out.wg3_last_n) TRY(run_wgrads(out.wg3_last, out.wg3_last_n, st));
+  if (out.score_words_last) {      // the word tasks of the score backward (the fused backward has scattered the item rows)
     ScoreArgs t = s;
     t.denc = nullptr; t.items_elsewhere = 1;
     TRY(launch_score_bwd(t, st));
   }
   TRY(side_join(st));
   return PS_OK;
+}
+
+extern "C" int ps_tem_backward(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
+                               float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
+                               ps_stream_t stream) {
+  EncBwdOut out;
+  const int rc = tem_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream, out);
+  enc_record_backward(out);
+  if (rc != PS_OK) side_abort();    // never leave the side stream waiting behind a failed call
+  return rc;
 }
 
 // ------------------------------------------------------------------ graph-replayed training step (graph.h)
