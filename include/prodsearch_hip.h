@@ -143,6 +143,34 @@ int ps_set_fuse_bwd_min(int rows);
  * the previous value.  ps_item_scatter_fused_taken: 1 when the last backward of this process took it. */
 int ps_set_item_scatter_fused(int on);
 int ps_item_scatter_fused_taken(void);
+/* Which kernels an item-transformer step launches (no reference counterpart; csrc/encoder.h, EncPlan): one attention form per
+ * layer and the forms of the steps around it.  Forward: rowlist (K / V products over the valid-row list), fwd_fuse_last (the
+ * last layer's Wo + LN + FFN + final LN as one kernel), fold_score (... with item scoring and the loss in its epilogue).
+ * Backward: fuse_last (the last layer's per-replica backward as one kernel), item_scatter (... which scatters the item rows),
+ * wg3_main / wg3_last (its K / V / Q weight gradients on the main stream / as the caller's last launches), wgrad_early (unfused
+ * form: W2 / W1 weight gradients forked as soon as d a1 exists), q_folded (dQ.Wq in the attention backward's tail), listed
+ * (dK / dV consumers walk the valid-row list), presum (the replicas' fan-in summed by its own launch), dx_fused (no dX product:
+ * the attention backward leaves d x as two partial rows). */
+typedef struct PsEncPath {
+  int32_t n_layers;
+  int32_t attn[PS_MAX_LAYERS];     /* AttnForm per layer: 0 generic, 1 sq1, 2 w1, 3 wf, 4 kvq */
+  int32_t rowlist, fwd_fuse_last, fold_score;
+  int32_t bwd_fuse_last, item_scatter, wg3_main, wg3_last, wgrad_early, q_folded, listed, presum, dx_fused;
+  int32_t wf_key_split;            /* taken record only: the WF backward launched attn_bwd_wk_kernel */
+} PsEncPath;
+/* The plan of the call this descriptor describes (C == 0: a training-mode forward / backward, C > 0: an eval scoring call), under
+ * the process's switches and setters.  Host only: no HIP call, works without a device — the plan reads the descriptor, the
+ * workspace layout, which tensors are null and the switches, and never dereferences a tensor or the workspace.  params NULL:
+ * every tensor present.  has_valid: the layer loops get a key-padding mask (the review transformer's callers; 0 here). */
+int ps_tem_plan(const PsTemDesc* desc, const PsTemTensors* params, int32_t has_valid, PsEncPath* out);
+/* What the last encoder forward (backward = 0: any entry point that encodes, eval calls included) or backward (backward = 1)
+ * of this process really launched: every field is set at the branch that launches, none is copied from the plan; the fields of
+ * the other direction are 0, and a backward reads the kvq form as wf (3).  Two fields are inferred at their branch rather than
+ * seen at a launch: rowlist is set with the kvq launch (whose workgroups project their sequence's valid positions only; the form
+ * exists only under the row list), and wg3_last where the three weight-gradient problems are handed to the caller, which
+ * launches them behind its embedding scatter.  A non-encoder model leaves n_layers = 0.  Under
+ * graph replay the record is that of the capture.  item_scatter equals ps_item_scatter_fused_taken(). */
+int ps_enc_path_taken(int32_t backward, PsEncPath* out);
 /* Tuning knob: how the backward's side stream crosses the main stream.  Bit 1: a join is a stream write-value / wait-value
  * pair instead of an event pair; bit 0: a fork is a wait-value on the side stream whose value the NEXT kernel launched on the
  * main stream stores as its first workgroup starts (every earlier main-stream kernel has completed by then) — the main stream

@@ -52,6 +52,12 @@ class PsTemWsLayout(C.Structure):
                                          'item_scores', 'word_scores', 'loss_parts', 'denc', 'dx')]
 
 
+class PsEncPath(C.Structure):
+    _fields_ = [('n_layers', C.c_int32), ('attn', C.c_int32 * PS_MAX_LAYERS)] + \
+               [(n, C.c_int32) for n in ('rowlist', 'fwd_fuse_last', 'fold_score', 'bwd_fuse_last', 'item_scatter', 'wg3_main',
+                                         'wg3_last', 'wgrad_early', 'q_folded', 'listed', 'presum', 'dx_fused', 'wf_key_split')]
+
+
 class PsAdamHyper(C.Structure):
     _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
                 ('weight_decay', C.c_float), ('max_grad_norm', C.c_float), ('noam', C.c_int32),
@@ -112,6 +118,8 @@ SYMBOLS = {
     'ps_set_fuse_bwd_min': (C.c_int, [C.c_int]),
     'ps_set_item_scatter_fused': (C.c_int, [C.c_int]),
     'ps_item_scatter_fused_taken': (C.c_int, []),
+    'ps_tem_plan': (C.c_int, [C.POINTER(PsTemDesc), C.POINTER(PsTemTensors), C.c_int32, C.POINTER(PsEncPath)]),
+    'ps_enc_path_taken': (C.c_int, [C.c_int32, C.POINTER(PsEncPath)]),
     'ps_set_side_mode': (C.c_int, [C.c_int]),
     'ps_side_values_in_use': (C.c_int, []),
     'ps_set_deterministic': (C.c_int, [C.c_int]),

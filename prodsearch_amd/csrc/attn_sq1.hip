@@ -1392,7 +1392,7 @@ int launch_attn_fwd_wf(const AttnArgs& a, uint32_t* amask, hipStream_t st) {
   PS_LAUNCH_CHECK();
   return PS_OK;
 }
-int launch_attn_bwd_wf(const AttnArgs& a, const uint32_t* amask, bool pads_unread, hipStream_t st) {
+int launch_attn_bwd_wf(const AttnArgs& a, const uint32_t* amask, bool pads_unread, hipStream_t st, bool* key_split) {
   PS_REQUIRE(attn_wf_fits(a) && amask, "attention bwd(wf): unsupported shape");
   PS_REQUIRE(!a.wq || (a.dxq_part && a.d == 128), "attention bwd(wf): folded dQ.Wq needs d == 128 and its output row buffer");
   PS_REQUIRE(!a.kvb_stream || (a.wq && a.dxp[0] && a.dxp[1] && a.d == 128), "attention bwd(wf): fused d x needs the folded dQ.Wq form and both partial buffers");
@@ -1404,7 +1404,10 @@ int launch_attn_bwd_wf(const AttnArgs& a, const uint32_t* amask, bool pads_unrea
   if (ps_diag_int("PS_ABW_STAMP", 0)) stamp = ps_debug_stamp_ptr();
 #endif
   static const bool wk_on = ps_env_int("PS_ATTN_WK", 1) != 0;       // d = 256: keys, not replicas, across the waves (0: the replica-split form)
-  if (a.dh == 32 && wk_on && !a.wq) hipLaunchKernelGGL((attn_bwd_wk_kernel<32, 3>), dim3(a.n_in * 2), dim3(256), 0, st, b, amask, pads_unread ? 1 : 0);
+  if (a.dh == 32 && wk_on && !a.wq) {
+    hipLaunchKernelGGL((attn_bwd_wk_kernel<32, 3>), dim3(a.n_in * 2), dim3(256), 0, st, b, amask, pads_unread ? 1 : 0);
+    if (key_split) *key_split = true;
+  }
   else if (a.dh == 32) hipLaunchKernelGGL((attn_bwd_wf4_kernel<32, 6, 2>), dim3(a.n_in * 2), dim3(256), 0, st, b, amask, pads_unread ? 1 : 0, stamp);
   else if (a.S <= 24) hipLaunchKernelGGL((attn_bwd_wf4_kernel<16, 6, 1>), dim3(a.n_in * 2), dim3(256), 0, st, b, amask, pads_unread ? 1 : 0, stamp);
   else hipLaunchKernelGGL((attn_bwd_wf4_kernel<16, 8, 1>), dim3(a.n_in * 2), dim3(256), 0, st, b, amask, pads_unread ? 1 : 0, stamp);

@@ -54,6 +54,8 @@ struct EncPlan {
     bool fuse_last;         // the last layer's whole per-replica backward as one kernel; needs the caller's ColFoldList
     bool item_scatter;      // ... which may scatter the item rows' gradients too (ps_set_item_scatter_fused; never deterministic)
     bool wg3_main;          // ... and whose K / V / Q weight gradients follow the dX product on the main stream
+                            //     (only while the layer's K / V rows are at most twice its replica rows, n_in * S <= 2 * M2: a longer
+                            //     product goes to the side stream, as the review transformer's 78k rows against 1.5k do)
     bool wg3_last;          // ... as the caller's last launches, where it flushes them (EncBwdIn::caller_flushes_tail)
     bool wgrad_early;       // unfused form: W2 / W1 weight gradients fork as soon as d a1 exists
     bool q_folded;          // layer 0: dQ.Wq rides in the attention backward's tail
@@ -64,7 +66,13 @@ struct EncPlan {
 };
 // `rows_listed`: w.vrows / w.vcount hold the list of valid (non-pad) rows of x (EmbedArgs::vrows, or the review transformer's
 // rtm_rowlist_kernel).  `valid`: the key-padding mask the layer loops will get (below); null for u_item_idxs.
+// enc_plan reads which tensors of P are null and the offsets in w, and builds addresses from ws; it never dereferences a
+// tensor or ws (ps_tem_plan calls it without a device).
 EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed, const float* valid);
+// What the layer loops really launched (ps_enc_path_taken): one record per direction, cleared where a direction's call starts
+// and filled at the launching branches — host bookkeeping, never read by the step itself.
+PsEncPath& enc_taken(int backward);
+void enc_taken_clear(int backward, int n_layers);
 
 // All encoder layers + the final LayerNorm on the consumed position: reads w.x, writes w.enc.
 // Key-padding mask: `valid` [n_seq, S] floats if given, else u_item_idxs != P (TEM).
@@ -96,7 +104,7 @@ struct EncBwdOut {
   bool score_words_last = false;       // ... and, when the fused backward has scattered the item rows, the score backward's word tasks behind them
   bool item_scatter_taken = false;     // the fused kernel scattered the item rows
 };
-void enc_record_backward(const EncBwdOut& out);   // once per backward entry point: what ps_item_scatter_fused_taken() reports
+void enc_record_backward(const EncBwdOut& out);   // once per backward entry point: what ps_item_scatter_fused_taken() reports (the taken record's item_scatter)
 int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui,
                         const float* valid, float* ws, const Ws& w, hipStream_t st, const EncBwdIn& in, EncBwdOut& out);
 

@@ -272,7 +272,8 @@ int launch_attn_bwd_w1(const AttnArgs& a, bool pads_unread, hipStream_t st);
 int launch_attn_fwd_w1(const AttnArgs& a, hipStream_t st);
 bool attn_wf_fits(const AttnArgs& a);      // one wave per (sequence, four heads), dropout replicas inside (S <= 32)
 int launch_attn_fwd_wf(const AttnArgs& a, uint32_t* amask, hipStream_t st);
-int launch_attn_bwd_wf(const AttnArgs& a, const uint32_t* amask, bool pads_unread, hipStream_t st);
+// `key_split` (optional): set when the d = 256 form with the keys across the waves (attn_bwd_wk_kernel) is the one launched
+int launch_attn_bwd_wf(const AttnArgs& a, const uint32_t* amask, bool pads_unread, hipStream_t st, bool* key_split = nullptr);
 bool attn_bwd_wf_two_partials(const AttnArgs& a);   // ... and its backward leaves two partial dQ.Wq rows per sequence
 int attn_sq1_split(const AttnArgs& a);   // head groups (workgroups) per sequence the sq1 kernels will use
 

@@ -787,6 +787,8 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
                        const Ws& w, hipStream_t st, const EncFwdOpts& o) {
   const int d = D.d, S = w.S, NL = D.n_layers;
   const EncPlan pl = enc_plan(D, P, ws, w, o.rows_listed, valid);
+  enc_taken_clear(0, NL);
+  PsEncPath& tk = enc_taken(0);
   for (int i = 0; i < NL; ++i) {
     const LayerWs& l = w.layer[i];
     const PsLayerTensors& Lp = P.layer[i];
@@ -813,6 +815,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       q.bk = Lp.bk; q.bv = Lp.bv; q.wq = Lp.wq; q.bq = Lp.bq;
       q.kp = ws + l.kp; q.vp = ws + l.vp; q.qp = ws + l.qp; q.amask = amask;
       TRY(launch_kvq_attn_fwd(q, st));
+      tk.attn[i] = ATTN_KVQ; tk.rowlist = 1;         // (its workgroups project their sequence's valid positions only)
     } else {   // K, V, Q projections (neural.py:192-197), Q pre-divided by sqrt(dh) (:206)
       GemmGroup g;
       memset(&g, 0, sizeof(g));
@@ -828,13 +831,14 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
         const int32_t* vc = reinterpret_cast<const int32_t*>(ws + w.vcount);
         g.p[0].ridx = vr; g.p[0].rcount = vc;
         g.p[1].ridx = vr; g.p[1].rcount = vc;
+        tk.rowlist = 1;
       }
       TRY(ps_launch_gemm(g, st));
       switch (pl.attn[i]) {
-        case ATTN_WF: TRY(launch_attn_fwd_wf(a, amask, st)); break;
-        case ATTN_W1: TRY(launch_attn_fwd_w1(a, st)); break;
-        case ATTN_SQ1: TRY(launch_attn_fwd_sq1(a, st)); break;
-        default: TRY(launch_attn_fwd(a, st));
+        case ATTN_WF: TRY(launch_attn_fwd_wf(a, amask, st)); tk.attn[i] = ATTN_WF; break;
+        case ATTN_W1: TRY(launch_attn_fwd_w1(a, st)); tk.attn[i] = ATTN_W1; break;
+        case ATTN_SQ1: TRY(launch_attn_fwd_sq1(a, st)); tk.attn[i] = ATTN_SQ1; break;
+        default: TRY(launch_attn_fwd(a, st)); tk.attn[i] = ATTN_GENERIC;
       }
     }
     const bool fuse = pl.fwd_fuse_last && i == NL - 1;
@@ -853,6 +857,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       if (o.fold_sc) { m.fold_score = 1; m.sc = *o.fold_sc; }
       m.x3 = make_wsplit(D, P, ws, w);
       TRY(launch_mlp_fwd_fused(m, st));
+      tk.fwd_fuse_last = 1; tk.fold_score = m.fold_score;
       continue;
     }
     {   // final_linear + dropout + residual (neural.py:228-231, transformer.py:56)
@@ -901,6 +906,7 @@ static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTem
   const bool tem = D.model == PS_MODEL_TEM;
   const int B = D.B, d = D.d, S = w.S;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
+  enc_taken_clear(0, 0);                        // (QEM / AEM / ZAM: no encoder layers; enc_layers_forward fills it otherwise)
   PS_REQUIRE(P.word_emb && P.product_emb && hist, "forward: null embedding table");
   EmbedArgs e;
   memset(&e, 0, sizeof(e));
@@ -1095,9 +1101,21 @@ extern "C" int ps_set_fuse_bwd_min(int rows) { return std::exchange(fuse_bwd_min
 // Deterministic mode never takes it (its sole-owner scatter walks the item tasks in order).
 static int& item_scatter_fused_slot() { static int v = ps_env_int("PS_ITEM_SCATTER_FUSED", 1); return v; }
 extern "C" int ps_set_item_scatter_fused(int on) { return std::exchange(item_scatter_fused_slot(), on); }
-static int g_item_scatter_taken = 0;     // the last backward's fused kernel scattered the item rows
-extern "C" int ps_item_scatter_fused_taken(void) { return g_item_scatter_taken; }
-void enc_record_backward(const EncBwdOut& out) { g_item_scatter_taken = out.item_scatter_taken ? 1 : 0; }
+// What the last forward [0] / backward [1] launched (encoder.h, enc_taken); item_scatter: the fused kernel scattered the item rows
+static PsEncPath g_taken[2];
+PsEncPath& enc_taken(int backward) { return g_taken[backward ? 1 : 0]; }
+void enc_taken_clear(int backward, int n_layers) {
+  PsEncPath& t = enc_taken(backward);
+  memset(&t, 0, sizeof(t));
+  t.n_layers = n_layers;
+}
+extern "C" int ps_item_scatter_fused_taken(void) { return g_taken[1].item_scatter; }
+void enc_record_backward(const EncBwdOut& out) { g_taken[1].item_scatter = out.item_scatter_taken ? 1 : 0; }
+extern "C" int ps_enc_path_taken(int32_t backward, PsEncPath* out) {
+  PS_REQUIRE(out, "enc_path_taken: null argument");
+  *out = enc_taken(backward);
+  return PS_OK;
+}
 
 // The switches are read once, here; the setters' slots (ps_set_fuse_bwd_min, ps_set_item_scatter_fused, ps_set_deterministic)
 // on every call.
@@ -1159,6 +1177,32 @@ EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws&
   return pl;
 }
 
+extern "C" int ps_tem_plan(const PsTemDesc* desc, const PsTemTensors* params, int32_t has_valid, PsEncPath* out) {
+  PS_REQUIRE(desc && out, "plan: null argument");
+  PsTemDesc D = *desc;
+  if (D.C > 0) D.training = 0;                  // an eval call (ps_tem_score); C == 0: ps_tem_forward / ps_tem_backward
+  Ws w;
+  TRY(make_ws(D, w));
+  // enc_plan tests pointers against null and adds offsets to the workspace base, nothing more: stand-ins that are never read
+  static float stand_in[4];
+  PsTemTensors all;
+  memset(&all, 0, sizeof(all));
+  if (!params) {
+    const float** slot = reinterpret_cast<const float**>(&all);
+    for (size_t k = 0; k < sizeof(all) / sizeof(float*); ++k) slot[k] = stand_in;
+  }
+  const EncPlan pl = enc_plan(D, params ? *params : all, stand_in, w, rows_list_ok(D), has_valid ? stand_in : nullptr);
+  memset(out, 0, sizeof(*out));
+  const bool enc = D.model == PS_MODEL_TEM && D.n_layers > 0;
+  out->n_layers = enc ? D.n_layers : 0;
+  for (int i = 0; i < out->n_layers; ++i) out->attn[i] = pl.attn[i];
+  out->rowlist = pl.rowlist; out->fwd_fuse_last = pl.fwd_fuse_last; out->fold_score = pl.fold_score;
+  out->bwd_fuse_last = pl.bwd.fuse_last; out->item_scatter = pl.bwd.item_scatter; out->wg3_main = pl.bwd.wg3_main;
+  out->wg3_last = pl.bwd.wg3_last; out->wgrad_early = pl.bwd.wgrad_early; out->q_folded = pl.bwd.q_folded;
+  out->listed = pl.bwd.listed; out->presum = pl.bwd.presum; out->dx_fused = pl.bwd.dx_fused;
+  return PS_OK;
+}
+
 // What the three sequences of the encoder backward share
 struct EncBwd {
   const PsTemDesc& D; const PsTemTensors& P; const PsTemTensors& G; float* ws; const Ws& w; hipStream_t st;
@@ -1210,6 +1254,7 @@ static int bwd_fused_last(const EncBwd& c, const ScoreArgs* score) {
   // the fused kernel below, its fork carried by that kernel: starved by 252 workgroups that own their CUs' LDS it took
   // 74 us instead of 29 and slowed the attention backward behind it, 0.278 -> 0.282 ms/step)
   TRY(launch_mlp_bwd_fused(m, st));
+  enc_taken(1).bwd_fuse_last = 1;
   TRY(side_fork(st));                           // fork 1: W2, W1, Wo weight gradients under the attention backward
   if (score && m.g_product_emb) {
     // the fused kernel above has added the item rows: what is left of the score backward are its word tasks (2 B workgroups,
@@ -1265,6 +1310,7 @@ static int bwd_ffn(const EncBwd& c, int i) {
     TRY(side_fork(st));
     TRY(side_run(wg, 1, st));
     TRY(side_run(wg1, 1, st));
+    enc_taken(1).wgrad_early = 1;
   }
   LnBwdArgs n;
   memset(&n, 0, sizeof(n));
@@ -1317,13 +1363,25 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
     a.bias_part = park(fold, ws + w.abpart + (size_t)i * w.layer[D.n_layers - 1].n_in * 3 * d, l.n_in, d, Lg.bq, Lg.bk, Lg.bv);
   // the first layer's forms (EncPlan::Bwd); listed / presum / dx_fused: one-layer encoders only
   const bool q_folded = i == 0 && pb.q_folded, listed = pb.listed, presum = pb.presum, dx_fused = pb.dx_fused;
-  if (q_folded) { a.wq = Lp.wq; a.dxq_part = ws + w.dln1; a.fanin_src = ws + w.dy1; }
-  if (dx_fused) { a.kvb_stream = make_wsplit(D, c.P, ws, w).bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; }
+  PsEncPath& tk = enc_taken(1);
+  if (q_folded) { a.wq = Lp.wq; a.dxq_part = ws + w.dln1; a.fanin_src = ws + w.dy1; tk.q_folded = 1; }
+  if (dx_fused) { a.kvb_stream = make_wsplit(D, c.P, ws, w).bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; tk.dx_fused = 1; }
   c.out.dx_two_partials = dx_fused;
   const bool pads_unread = listed && (q_folded || l.fan == 1 || presum);
-  if (wf) TRY(launch_attn_bwd_wf(a, reinterpret_cast<const uint32_t*>(ws + l.amask), pads_unread, st));
-  else if (w1) TRY(launch_attn_bwd_w1(a, pads_unread, st));
-  else TRY(form == ATTN_SQ1 ? launch_attn_bwd_sq1(a, st) : launch_attn_bwd(a, st));
+  if (wf) {
+    bool key_split = false;
+    TRY(launch_attn_bwd_wf(a, reinterpret_cast<const uint32_t*>(ws + l.amask), pads_unread, st, &key_split));
+    tk.attn[i] = ATTN_WF; tk.wf_key_split = key_split ? 1 : 0;
+  } else if (w1) {
+    TRY(launch_attn_bwd_w1(a, pads_unread, st));
+    tk.attn[i] = ATTN_W1;
+  } else if (form == ATTN_SQ1) {
+    TRY(launch_attn_bwd_sq1(a, st));
+    tk.attn[i] = ATTN_SQ1;
+  } else {
+    TRY(launch_attn_bwd(a, st));
+    tk.attn[i] = ATTN_GENERIC;
+  }
   // weight gradients of Wo, Wk, Wv, Wq: one fork right behind the attention backward, off the dX chain
   GemmProblem wg3[3];
   wg3[0] = gp_wgrad(ws + w.dkv, a.lddkv, xn, d, Lg.wk, d, d, ns);
@@ -1353,6 +1411,7 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
   if (listed) {
     wg3[0].ridx = vr; wg3[0].rcount = vc;
     wg3[1].ridx = vr; wg3[1].rcount = vc;
+    tk.listed = 1;
   }
   if (!wg3_main) {
     TRY(side_fork(st));
@@ -1376,6 +1435,7 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
     if (presum) {   // fan-in summed up front: one row per sequence beside the dQ.Wq row, nothing to walk
       float* fsum = ws + w.dln1;          // (free: the FF LayerNorm backward has consumed d ln1)
       TRY(launch_fanin_sum(ws + w.dy1, d, l.n_in, l.fan, d, fsum, st));
+      tk.presum = 1;
       x.res.ptr = nullptr; x.res.extra = dxq; x.res.extra2 = fsum; x.res.extra_ld = d;
     }
   }
@@ -1384,7 +1444,8 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
   if (pads_unread) { x.ridx = vr; x.rcount = vc; }
   if (!dx_fused) TRY(run1(x, st));
   if (wg3_main) {
-    if (pb.wg3_last && c.in.caller_flushes_tail) { for (int q = 0; q < 3; ++q) c.out.wg3_last[q] = wg3[q]; c.out.wg3_last_n = 3; }
+    tk.wg3_main = 1;
+    if (pb.wg3_last && c.in.caller_flushes_tail) { for (int q = 0; q < 3; ++q) c.out.wg3_last[q] = wg3[q]; c.out.wg3_last_n = 3; tk.wg3_last = 1; }
     else TRY(run_wgrads(wg3, 3, st));
   }
   if (!qall && !q_via_res) {
@@ -1401,6 +1462,7 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
   PS_REQUIRE(G.final_ln_g && G.final_ln_b, "backward: null final LayerNorm gradient");
   const EncPlan pl = enc_plan(D, P, ws, w, in.rows_listed, valid);
   out = EncBwdOut();
+  enc_taken_clear(1, NL);
   const EncBwd c = {D, P, G, ws, w, st, pl, in, out};
   const bool fuse_last = pl.bwd.fuse_last;
   side_set_light((int64_t)B * S * d <= ((int64_t)2 << 20));   // C2: 1.03 M elements of x; review transformer 10 M; C5 5.5 M
@@ -1474,6 +1536,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
                              float* ws, const PsTemTensors* grads, float loss_scale, const float* loss_scale_dev,
                              ps_stream_t stream, EncBwdOut& out) {
   PS_REQUIRE(desc && params && batch && ws && grads, "backward: null argument");
+  enc_taken_clear(1, 0);                          // (QEM / AEM / ZAM: no encoder layers; enc_layers_backward fills it otherwise)
   PsTemDesc D = *desc;
   D.C = 0;
   Ws w;

@@ -3,9 +3,18 @@ BASELINE configs[4] — and d=512, both through the module API.  Tolerances as t
 import pytest
 import torch
 
+import enc_paths
 from golden_util import rel_err
 
 pytestmark = pytest.mark.gpu
+
+
+def edge_row(B, K, L, Q, W, d, H, zero_hist, dropout):
+    """The enc_paths row of an edge-shape case."""
+    key = dict(B=B, K=K, L=L, Q=Q, W=W, d=d, H=H, zero_hist=zero_hist, dropout=dropout)
+    hit = [r for r in enc_paths.EDGE_ROWS if all(r[k] == v for k, v in key.items())]
+    assert len(hit) == 1, key                      # every edge case has its row
+    return hit[0]
 
 
 @pytest.mark.parametrize('d,F,B,K,dropout', [(256, 1024, 24, 6, 0.0), (512, 1024, 9, 4, 0.0), (256, 1024, 16, 5, 0.1),
@@ -13,8 +22,9 @@ pytestmark = pytest.mark.gpu
                                              (512, 1024, 300, 3, 0.0)])   # 6,300 K/V rows, few splits: row-list weight gradients remap their split count
 def test_wide_embeddings_match_oracle(d, F, B, K, dropout):
     from oracle import tem as otem, philox
-    from prodsearch_amd import ItemTransformerRanker, default_args, synth
+    from prodsearch_amd import ItemTransformerRanker, _lib, default_args, synth
     P_, V = 3000, 2000
+    row = enc_paths.WIDE_ROWS.get((d, B, K, dropout))     # the encoder path of the annotated cases
     a = default_args(model_name='item_transformer', embedding_size=d, ff_size=F, heads=8, inter_layers=1,
                      neg_per_pos=K, dropout=dropout, uprev_review_limit=20)
     wd = synth.make_word_dists(V)
@@ -25,9 +35,13 @@ def test_wide_embeddings_match_oracle(d, F, B, K, dropout):
     batch = synth.make_tem_batch(3, B, P_, V, Q=8, L=20, W=1, word_dists=wd)
     ni, nw = synth.sample_negatives(4, B, K, 1, P_, wd)
     loss = m(batch.to('cuda'), neg_item_idxs=ni.cuda(), neg_word_idxs=nw.cuda())
+    if row:
+        enc_paths.assert_taken(_lib.load(), row, 0)
     m.zero_grad()
     loss.backward()
     torch.cuda.synchronize()
+    if row:
+        enc_paths.assert_taken(_lib.load(), row, 1)
     Pm = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     kw = {}
     if dropout > 0:
@@ -65,12 +79,13 @@ def test_wide_embeddings_match_oracle(d, F, B, K, dropout):
     (6, 4, 40, 4, 1, 128, 8, 0.1, 0.0),      # ... no replicas: one wave per sequence, 32 lanes per row
     (6, 4, 40, 4, 1, 64, 4, 0.1, 0.0),       # ... and 16 lanes per row (d = 64)
 ])
-def test_edge_shapes_match_oracle(B, K, L, Q, W, d, H, zero_hist, dropout):
+def test_edge_shapes_match_oracle(B, K, L, Q, W, d, H, zero_hist, dropout, row=None):
     """Edge cases of the batch layout: tiny and ragged batches, zero-history users,
     padded pv windows, wide negative fans — loss, gradients, touched rows and eval scores against the oracle."""
     from oracle import tem as otem, philox
-    from prodsearch_amd import ItemTransformerRanker, default_args, synth
+    from prodsearch_amd import ItemTransformerRanker, _lib, default_args, synth
     P_, V = 700, 900
+    row = row or edge_row(B, K, L, Q, W, d, H, zero_hist, dropout)     # (a caller under another setting passes its own)
     a = default_args(model_name='item_transformer', embedding_size=d, ff_size=2 * d, heads=H, inter_layers=1,
                      neg_per_pos=K, dropout=dropout, uprev_review_limit=L, pv_window_size=W)
     wd = synth.make_word_dists(V)
@@ -83,9 +98,13 @@ def test_edge_shapes_match_oracle(B, K, L, Q, W, d, H, zero_hist, dropout):
         assert int((batch.u_item_idxs != P_).sum()) == 0
     ni, nw = synth.sample_negatives(12, B, K, W, P_, wd)
     loss = m(batch.to('cuda'), neg_item_idxs=ni.cuda(), neg_word_idxs=nw.cuda())
+    if row:
+        enc_paths.assert_taken(_lib.load(), row, 0)
     m.zero_grad()
     loss.backward()
     torch.cuda.synchronize()
+    if row:
+        enc_paths.assert_taken(_lib.load(), row, 1)
     Pm = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     kw = {}
     if dropout > 0:
@@ -120,7 +139,7 @@ def test_fused_backward_partial_tiles(B, K, L, Q, W, zero_hist):
     from prodsearch_amd import _lib
     old = _lib.load().ps_set_fuse_bwd_min(1)
     try:
-        test_edge_shapes_match_oracle(B, K, L, Q, W, 128, 8, zero_hist, 0.1)
+        test_edge_shapes_match_oracle(B, K, L, Q, W, 128, 8, zero_hist, 0.1, row=enc_paths.PARTIAL_TILE_ROWS[(B, K, L)])
     finally:
         _lib.load().ps_set_fuse_bwd_min(old)
 

@@ -13,9 +13,10 @@ from golden_util import rel_err
 pytestmark = pytest.mark.gpu
 
 
-def check_against_oracle(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, **over):
+def check_against_oracle(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, expect=None, **over):
     """One training forward + backward through the module API and one eval call, against oracle.tem.  ``over``: default_args
-    overrides on top of d = 128, 8 heads, ff 256, one layer, dropout 0.1."""
+    overrides on top of d = 128, 8 heads, ff 256, one layer, dropout 0.1.  ``expect``: called with 0 behind the training forward
+    and with 1 behind the backward (enc_paths.taken_checker: the encoder path the step took)."""
     from oracle import tem as otem, philox
     from prodsearch_amd import ItemTransformerRanker, default_args, synth
     kw = dict(model_name='item_transformer', embedding_size=128, heads=8, ff_size=256, inter_layers=1, neg_per_pos=K,
@@ -31,9 +32,13 @@ def check_against_oracle(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, **over):
     batch = synth.make_tem_batch(11, B, P_, V, Q=Q, L=L, W=W, C=9, word_dists=wd, zero_hist_frac=zero_hist)
     ni, nw = synth.sample_negatives(12, B, K, W, P_, wd)
     loss = m(batch.to('cuda'), neg_item_idxs=ni.cuda(), neg_word_idxs=nw.cuda())
+    if expect:
+        expect(0)
     m.zero_grad()
     loss.backward()
     torch.cuda.synchronize()
+    if expect:
+        expect(1)
 
     Pm = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     drop = None
@@ -44,17 +49,23 @@ def check_against_oracle(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, **over):
         oloss, _, _ = otem.qem_forward(Pm, a, batch, ni, nw, V, P_, training=True, drop=drop)
     else:
         oloss, _, _ = otem.tem_forward(Pm, a, batch, ni, nw, V, P_, training=True, replicate=drop is not None, drop=drop)
+    print('figures: loss rel_err %.2e' % rel_err(loss.detach().cpu(), oloss.detach()))
     assert rel_err(loss.detach().cpu(), oloss.detach()) < 1e-4
     grads = otem.grads_of(oloss, Pm, otem.tem_pad_rows(a, V, P_))
+    worst = (0.0, None)
     for n, p in m.named_parameters():
         ref = grads.get(n)
         assert (p.grad is None) == (ref is None), n
         if ref is None or n.endswith('linear_keys.bias'):       # (its gradient is rounding noise: softmax is shift-invariant)
             continue
         got = p.grad.cpu()
-        assert rel_err(got, ref) < 5e-4, (n, rel_err(got, ref))
+        err = rel_err(got, ref)
+        assert err < 5e-4, (n, err)
+        if err >= worst[0]:
+            worst = (float(err), n)
         if ref.dim() == 2 and ref.shape[0] > 256:
             assert torch.equal(got.ne(0).any(1), ref.ne(0).any(1)), n
+    print('figures: worst gradient rel_err %.2e (%s)' % worst)
     # the query words' rows alone: their gradient shares word_embeddings with item_to_words', and a wrong query part can hide
     # under the whole table's largest entry
     qrows = torch.unique(batch.query_word_idxs)
@@ -91,7 +102,9 @@ CASES = {
 
 @pytest.mark.parametrize('case', list(CASES))
 def test_option_matches_oracle(case):
-    check_against_oracle(**CASES[case])
+    import enc_paths
+    row = enc_paths.OPTION_ROWS.get(case)          # the encoder path of the annotated cases
+    check_against_oracle(expect=enc_paths.taken_checker(row) if row else None, **CASES[case])
 
 
 def test_avg_deterministic_matches_oracle():
