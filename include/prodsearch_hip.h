@@ -464,7 +464,15 @@ typedef struct PsRtmDesc {
   int32_t use_item_emb;  /*   to every sequence (ps_model.py:325-334, :229-234)                         */
   int64_t user_size;     /* pad user = user_size, pad item = product_size (ps_model.py:66-67)           */
   int64_t product_size;
+  /* appended (a zero-filled tail is the behaviour before them): */
+  int32_t frozen_mask;   /* PS_RTM_FROZEN_*: tables that take no gradient (nn.Embedding.from_pretrained, fix_emb,       */
+                         /*   requires_grad False); ps_rtm_backward wants exactly their gradient pointers NULL          */
+  int32_t no_pv_drop;    /* fix_emb (PV.py:36-39): PV.forward's own drop_layer has p = 0; dropout_layer still applies   */
 } PsRtmDesc;
+enum { PS_RTM_FROZEN_WORD = 1,     /* word_embeddings (= pvc's context_embeddings)            */
+       PS_RTM_FROZEN_REVIEW = 2,   /* review_encoder.review_embeddings (pv)                   */
+       PS_RTM_FROZEN_USER = 4,     /* user_emb (use_user_emb)                                 */
+       PS_RTM_FROZEN_ITEM = 8 };   /* product_emb (use_item_emb)                              */
 
 typedef struct PsRtmTensors {
   float *word_emb;       /* word_embeddings.weight [V,d] (= review_encoder.context_embeddings for pvc) */
@@ -526,9 +534,35 @@ int ps_rtm_workspace_layout(const PsRtmDesc* desc, int32_t eval, PsRtmWsLayout* 
 /* loss = model(batch, train_pv) -- ProductRanker.forward (ps_model.py:241-358); loss3 = {loss, ps_loss, pv_loss} */
 int ps_rtm_forward(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* workspace,
                    float* loss3, ps_stream_t stream);
-/* loss.backward() (trainer.py:77): accumulates into dense grads */
+/* loss.backward() (trainer.py:77): accumulates into dense grads.  grads->word_emb / review_emb / user_emb / product_emb NULL:
+ * that table is frozen and no kernel reads or writes a gradient row of it; the NULLs must agree with desc->frozen_mask (a table
+ * the configuration does not have — review_emb of pvc / fs / avg, user_emb without use_user_emb — is not checked). */
 int ps_rtm_backward(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* workspace,
                     const PsRtmTensors* grads, float loss_scale, const float* loss_scale_dev, ps_stream_t stream);
+/* What ps_rtm_backward runs for this descriptor, decided once (csrc/rtm.hip, rtm_bwd_plan; the backward reads this plan and
+ * nothing else).  Host only: no HIP call, works without a device; reads the descriptor, the workspace layout and the process's
+ * switches (ps_set_deterministic, PS_RTM_HIST). */
+enum { PS_RTM_INDEX_NONE = 0, PS_RTM_INDEX_HIST = 1,    /* LDS-histogram index on the side stream                        */
+       PS_RTM_INDEX_FWD_COUNTS = 2,                     /* counts + ranks from the forward's gather, fill on the side stream */
+       PS_RTM_INDEX_LATE = 3 };                         /* counted, allocated and filled behind the embed backward       */
+enum { PS_RTM_PV_NONE = 0, PS_RTM_PV_DVEC = 1, PS_RTM_PV_WORDS = 2, PS_RTM_PV_BOTH = 3 };
+enum { PS_RTM_EB_GENERAL = 0, PS_RTM_EB_PLAIN = 1,      /* rtm_embed_bwd_kernel<NK, 0 / 1>                               */
+       PS_RTM_EB_FROZEN = 2 };                          /* <NK, 2>: no review-side table takes a gradient                */
+typedef struct PsRtmBwdPlan {
+  int32_t index;          /* PS_RTM_INDEX_*: the inverted index word -> review slots (rtm_hist* / rtm_walloc / rtm_windex) */
+  int32_t word_reduce;    /* rtm_wreduce* sums the slot rows of every word into word_emb's gradient                        */
+  int32_t slot_rows;      /* the review slots of d x are rewritten in place as per-word (pv, deterministic: per-review) rows */
+  int32_t review_scatter; /* review rows are added into review_emb's gradient (atomics, or the sole-owner scatter)         */
+  int32_t pv_bwd;         /* PS_RTM_PV_*: which gradients of the PV loss exist (d vec -> the review side, the word rows)    */
+  int32_t pv_bwd_kernel;  /* rtm_pv_bwd_kernel is launched (deterministic + word rows only: rtm_pv_keys_kernel alone)      */
+  int32_t fs_draw;        /* fs: the d raw = d pre . f_W product                                                           */
+  int32_t query_scatter;  /* the query words' rows are scattered (and the unfused FS path builds d mean)                   */
+  int32_t user_scatter, item_scatter;
+  int32_t embed_form;     /* PS_RTM_EB_*                                                                                   */
+  int32_t slot_waves;     /* the embed backward launches review-slot waves (0: the query-position waves alone)             */
+  int32_t side_fork;      /* the backward forks its side stream for the index at its head                                  */
+} PsRtmBwdPlan;
+int ps_rtm_backward_plan(const PsRtmDesc* desc, PsRtmBwdPlan* out);
 /* scores = model.test(batch) [B,C] -- ProductRanker.test (ps_model.py:205-239) */
 int ps_rtm_score(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* workspace,
                  float* scores, ps_stream_t stream);

@@ -22,7 +22,8 @@ from .item_transformer import ItemTransformerRanker
 from .attn_embedding import AttentionEmbeddingRanker
 from .optimizers import Optimizer, build_optim
 from .ps_model import ProductRanker
+from .rtm_pretrained import PretrainedProductRanker
 from .rtm_data import ProdSearchTestBatch, ProdSearchTrainBatch
 
-__all__ = ['ProductRanker', 'ProdSearchTrainBatch', 'ProdSearchTestBatch', 'ItemTransformerRanker', 'AttentionEmbeddingRanker', 'Optimizer', 'build_optim', 'ItemPVBatch', 'default_args',
+__all__ = ['ProductRanker', 'PretrainedProductRanker', 'ProdSearchTrainBatch', 'ProdSearchTestBatch', 'ItemTransformerRanker', 'AttentionEmbeddingRanker', 'Optimizer', 'build_optim', 'ItemPVBatch', 'default_args',
            'readme_tem_args']

@@ -82,7 +82,19 @@ class PsRtmDesc(C.Structure):
                                          'pos_weight', 'train_pv', 'training')] + \
                [('dropout', C.c_float), ('corrupt_rate', C.c_float), ('seed', C.c_uint64), ('step', C.c_uint64)] + \
                [('use_user_emb', C.c_int32), ('use_item_emb', C.c_int32), ('user_size', C.c_int64),
-                ('product_size', C.c_int64)]
+                ('product_size', C.c_int64), ('frozen_mask', C.c_int32), ('no_pv_drop', C.c_int32)]
+
+
+PS_RTM_FROZEN_WORD, PS_RTM_FROZEN_REVIEW, PS_RTM_FROZEN_USER, PS_RTM_FROZEN_ITEM = 1, 2, 4, 8
+PS_RTM_INDEX_NONE, PS_RTM_INDEX_HIST, PS_RTM_INDEX_FWD_COUNTS, PS_RTM_INDEX_LATE = 0, 1, 2, 3
+PS_RTM_PV_NONE, PS_RTM_PV_DVEC, PS_RTM_PV_WORDS, PS_RTM_PV_BOTH = 0, 1, 2, 3
+PS_RTM_EB_GENERAL, PS_RTM_EB_PLAIN, PS_RTM_EB_FROZEN = 0, 1, 2
+
+
+class PsRtmBwdPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('index', 'word_reduce', 'slot_rows', 'review_scatter', 'pv_bwd', 'pv_bwd_kernel',
+                                         'fs_draw', 'query_scatter', 'user_scatter', 'item_scatter', 'embed_form',
+                                         'slot_waves', 'side_fork')]
 
 
 RTM_TOP_FIELDS = ('word_emb', 'review_emb', 'seg_emb', 'fs_w', 'fs_b', 'pe', 'final_ln_g', 'final_ln_b',
@@ -146,6 +158,7 @@ SYMBOLS = {
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     'ps_rtm_backward': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmTensors), C.POINTER(PsRtmBatch),
                                   C.c_void_p, C.POINTER(PsRtmTensors), C.c_float, C.c_void_p, C.c_void_p]),
+    'ps_rtm_backward_plan': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmBwdPlan)]),
     'ps_rtm_score': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmTensors), C.POINTER(PsRtmBatch),
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     'ps_rtm_review_embeddings': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmTensors), C.c_void_p,

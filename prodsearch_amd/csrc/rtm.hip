@@ -1069,6 +1069,10 @@ __global__ __launch_bounds__(256) void rtm_pv_keys_kernel(const RtmK a, int32_t*
 }
 
 // PV backward: one wave per positive review; d vec (dense) and word-row scatter-adds
+// WR = false: the word table is frozen — no word-row atomics (and in deterministic mode, where rtm_pv_keys_kernel scatters the
+// rows, this kernel only ever builds d vec).  DV = false: the review side takes no gradient (pv: a frozen review table; pvc's
+// d vec only ever reaches the word rows) — no word row is loaded and d vec is not stored.  <false, false> is never launched.
+template <bool WR, bool DV>
 __global__ __launch_bounds__(256) void rtm_pv_bwd_kernel(const RtmK a) {
   const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
   const int rev = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1089,15 +1093,16 @@ __global__ __launch_bounds__(256) void rtm_pv_bwd_kernel(const RtmK a) {
     const float s = a.pv_scores[((size_t)rev * a.W + w) * K1 + j];
     const float ds = (sigmoid_f(s) - (j == 0 ? 1.f : 0.f)) * sc;
     const float* wrow = a.word_emb + (size_t)idx * d;
-    float* grow = a.g_word_emb + (size_t)idx * d;
+    float* grow = WR ? a.g_word_emb + (size_t)idx * d : nullptr;
 #pragma unroll
     for (int k = 0; k < 16; ++k)
       if (k < epl) {
         const int e = c + 32 * k;
-        if (idx != a.V - 1 && !a.det) atomicAdd(&grow[e], ds * vec[e]);      // det: rtm_pv_keys_kernel + launch_rows_scatter_det
-        dv[k] += ds * wrow[e];
+        if (WR && idx != a.V - 1 && !a.det) atomicAdd(&grow[e], ds * vec[e]);      // det: rtm_pv_keys_kernel + launch_rows_scatter_det
+        if (DV) dv[k] += ds * wrow[e];
       }
   }
+  if (!DV) return;
 #pragma unroll
   for (int k = 0; k < 16; ++k)
     if (k < epl) {
@@ -1141,13 +1146,19 @@ __global__ __launch_bounds__(256) void rtm_ui_keys_kernel(const RtmK a, int32_t*
 // PL (the pvc encoder without the PV loss, the feature-selection layer and the user / item embeddings — configs[3]): those
 // switches are compile-time off, which takes their pointers and flags out of the scalar registers (the general form reloads 34
 // spilled scalars per group from VGPR lanes)
+// PL = 2, the frozen form: no review-side table takes a gradient (frozen words under pvc / fs / avg, a frozen
+// review table under pv).  A review-slot wave then only feeds d x into the segment partials and the trainable user / item rows:
+// no Philox word, no cnt / dvec / d raw load, no store to gs, no add to g_table — all compile-time off, as with PL = 1.  When
+// neither the segment rows nor user / item rows take a gradient the launcher passes npos_w = nneg_w = 0 and the grid is the
+// query-position waves alone.
 template <int NK, int PL>      // columns per lane: d <= 64 * NK
 __global__ __launch_bounds__(256) void rtm_embed_bwd_kernel(const RtmK a, float* seg_part, int npos_w, int nneg_w, FDiv fR, FDiv fK) {
   __shared__ float segs[4][3][64 * NK];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int wave = (int)blockIdx.x * 4 + wv;
   const int d = a.d;
-  const bool pvc = PL ? true : (bool)a.pvc, has_ui = !PL && !a.det && (a.g_user_emb || a.g_item_emb);   // det: rtm_ui_keys_kernel + launch_rows_scatter_det
+  constexpr bool FZ = PL == 2;
+  const bool pvc = PL == 1 ? true : (bool)a.pvc, has_ui = PL != 1 && !a.det && (a.g_user_emb || a.g_item_emb);   // det: rtm_ui_keys_kernel + launch_rows_scatter_det
   const float* const dmean = PL ? nullptr : a.dmean;
   const int64_t rpad = a.RC - 1;
   DropSpec dpos = a.d_pos, dneg = a.d_neg, dpv = a.d_pv;      // the step word is read once, not per element
@@ -1207,7 +1218,7 @@ __global__ __launch_bounds__(256) void rtm_embed_bwd_kernel(const RtmK a, float*
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
         Philox4 t = {0u, 0u, 0u, 0u};
-        if (ds.thr) t = philox4x32_10((uint32_t)(lane + 64 * k), (uint32_t)gg, ds.site, ds.step, ds.k0, ds.k1);
+        if (!FZ && ds.thr) t = philox4x32_10((uint32_t)(lane + 64 * k), (uint32_t)gg, ds.site, ds.step, ds.k0, ds.k1);
         dw[k][0] = t.x; dw[k][1] = t.y; dw[k][2] = t.z; dw[k][3] = t.w;
       }
       // every address is a real one (a dead row repeats the group's first, columns past d clamp), so the loads of the four
@@ -1217,6 +1228,12 @@ __global__ __launch_bounds__(256) void rtm_embed_bwd_kernel(const RtmK a, float*
       for (int q = 0; q < 4; ++q) {
         const float* g = a.dx + ((size_t)nq[q] * a.S + sq[q]) * d;
         // fs: the review vector reached x through tanh(f_W . raw + b); its input gradient d raw was left in a.dmean
+        if (FZ) {                                          // (compile-time) d x is all a frozen slot needs
+#pragma unroll
+          for (int k = 0; k < NK; ++k) { gk[q][k] = g[colc[k]]; src[q][k] = 0.f; dvv[q][k] = 0.f; }
+          cntv[q] = 1.f;
+          continue;
+        }
         const float* gm = dmean ? dmean + ((pos ? (size_t)0 : (size_t)a.B * a.R) + rrq[q]) * d : g;
         const float* dvp = wantdv ? a.dvec + (size_t)rrq[q] * d : g;
 #pragma unroll
@@ -1247,6 +1264,7 @@ __global__ __launch_bounds__(256) void rtm_embed_bwd_kernel(const RtmK a, float*
             else sacc[2][k] += v;
           }
         }
+        if (FZ) continue;                                  // (compile-time) nothing behind the review vector takes a gradient
         // through dropout_layer (and, pv positive with train_pv, the PV drop_layer + the PV-loss gradient)
         float t[NK];
 #pragma unroll
@@ -1763,6 +1781,10 @@ static void fill_k(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatch& 
   memset(&dd, 0, sizeof(dd));
   dd.training = k.training; dd.dropout = D.dropout; dd.seed = D.seed; dd.step = D.step;
   k.d_pv = make_drop(dd, SITE_REV_PV); k.d_pos = make_drop(dd, SITE_REV_POS); k.d_neg = make_drop(dd, SITE_REV_NEG);
+  if (D.no_pv_drop) {      // fix_emb: PV.forward's drop_layer has p = 0 (PV.py:36-39) — the site is the identity, forward and backward
+    dd.dropout = 0.f;
+    k.d_pv = make_drop(dd, SITE_REV_PV);
+  }
   dd.dropout = D.review_encoder == PS_RENC_PVC ? D.corrupt_rate : 0.f;
   k.t_pos = make_drop(dd, SITE_TOK_POS); k.t_neg = make_drop(dd, SITE_TOK_NEG);
   k.U = D.user_size; k.PI = D.product_size;
@@ -1797,9 +1819,9 @@ static void fill_k(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatch& 
 // pass (per-word counts, and with them every occurrence's rank inside its word) rides in the training forward when that
 // embeds through rtm_embed4_kernel, which holds every word id in registers; the backward then only allocates and fills,
 // on the side stream under its first kernels.
-static bool rtm_embed4_taken(const PsRtmDesc& D, const RtmK& k, const RtmWs& r) {
+static bool rtm_embed4_taken(const PsRtmDesc& D, bool eval, const RtmWs& r) {
   static const bool e4_on = ps_diag_int("PS_RTM_EMBED4", 1) != 0;
-  return e4_on && k.pvc && !k.eval && D.WL <= 128 && (D.d == 64 || D.d == 128 || D.d == 256) && r.S <= 64;
+  return e4_on && D.review_encoder != PS_RENC_PV && !eval && D.WL <= 128 && (D.d == 64 || D.d == 128 || D.d == 256) && r.S <= 64;
 }
 // (Round 3, measured and dropped: the whole index built on the side stream BESIDE the forward, so that the forward carries no
 // atomics.  Kernels of scattered global atomics poison whatever runs next to them: the gather launch stayed at 97 us without its
@@ -1807,15 +1829,57 @@ static bool rtm_embed4_taken(const PsRtmDesc& D, const RtmK& k, const RtmWs& r) 
 // rank atomics cost 45 of its 97 us — the fix is fewer global atomics, not a different place for them.)
 // the LDS-histogram index (rtm_hist_kernel): the backward builds the whole index on its side stream without global atomics and
 // the forward carries none.  PS_RTM_HIST=0: the round-2 form (ranks by global atomics in the forward's gather).
-static bool rtm_hist_index(const PsRtmDesc& D, const RtmK& k, const RtmWs& r) {
+static bool rtm_hist_index(const PsRtmDesc& D, const RtmWs& r) {
   static const bool on = ps_env_int("PS_RTM_HIST", 1) != 0;
   static const bool late = ps_diag_int("PS_RTM_LATE_INDEX", 0) != 0;
-  return on && !late && k.pvc && !k.eval && r.hist != 0 && D.vocab_size <= RTM_HIST_MAXV && r.S == D.R + 1 &&
+  return on && !late && D.review_encoder != PS_RENC_PV && r.hist != 0 && D.vocab_size <= RTM_HIST_MAXV && r.S == D.R + 1 &&
          ps_cdiv((int64_t)r.Bseq * D.R, RTM_HIST_G) <= (1 << 20);
 }
-static bool rtm_counts_in_forward(const PsRtmDesc& D, const RtmK& k, const RtmWs& r) {
+static bool rtm_counts_in_forward(const PsRtmDesc& D, const RtmWs& r) {
   static const bool late = ps_diag_int("PS_RTM_LATE_INDEX", 0) != 0;
-  return !late && !rtm_hist_index(D, k, r) && rtm_embed4_taken(D, k, r);
+  return !late && !rtm_hist_index(D, r) && rtm_embed4_taken(D, false, r);
+}
+
+// What one training backward runs, decided ONCE from the descriptor (its frozen mask included), the workspace layout and the
+// process's switches — like EncPlan for the layer loops (encoder.h).  rtm_backward_impl reads this and nothing else; the
+// training forward reads `index` (does its gather count word ranks?); ps_rtm_backward_plan hands it out (host only).
+//   review side = what sits behind a review vector: the word table for the word-mean encoders (pvc / fs / avg), the review
+//   table for pv.  When it is frozen nothing behind x's review slots takes a gradient (fs: f_W does, straight from d x).
+static PsRtmBwdPlan rtm_bwd_plan(const PsRtmDesc& D, const RtmWs& r, bool det) {
+  PsRtmBwdPlan p;
+  memset(&p, 0, sizeof(p));
+  const bool wordmean = D.review_encoder != PS_RENC_PV;
+  const bool words = !(D.frozen_mask & PS_RTM_FROZEN_WORD);
+  const bool reviews = !wordmean && !(D.frozen_mask & PS_RTM_FROZEN_REVIEW);
+  const bool side = wordmean ? words : reviews;
+  p.index = !(wordmean && words) ? PS_RTM_INDEX_NONE
+            : rtm_hist_index(D, r) ? PS_RTM_INDEX_HIST : (rtm_counts_in_forward(D, r) ? PS_RTM_INDEX_FWD_COUNTS : PS_RTM_INDEX_LATE);
+  p.word_reduce = wordmean && words;
+  p.slot_rows = p.word_reduce || (det && reviews);
+  p.review_scatter = reviews;
+  if (D.train_pv) {        // (pv / pvc only: rtm_check)
+    p.pv_bwd = (side ? PS_RTM_PV_DVEC : 0) | (words ? PS_RTM_PV_WORDS : 0);
+    p.pv_bwd_kernel = side || (words && !det);       // det: the word rows go through rtm_pv_keys_kernel + the sole-owner scatter
+  }
+  p.fs_draw = D.review_encoder == PS_RENC_FS && words;
+  p.query_scatter = words;
+  p.user_scatter = D.use_user_emb && !(D.frozen_mask & PS_RTM_FROZEN_USER);
+  p.item_scatter = D.use_item_emb && !(D.frozen_mask & PS_RTM_FROZEN_ITEM);
+  p.embed_form = !side ? PS_RTM_EB_FROZEN
+                 : (wordmean && D.review_encoder != PS_RENC_FS && !p.user_scatter && !p.item_scatter && !D.train_pv) ? PS_RTM_EB_PLAIN
+                                                                                                                   : PS_RTM_EB_GENERAL;
+  // frozen form: a review-slot wave feeds the segment partials and (by atomics; deterministic mode scatters them beforehand) the
+  // user / item rows — with none of them there is nothing for it to do
+  p.slot_waves = p.embed_form != PS_RTM_EB_FROZEN || D.use_seg_emb || (!det && (p.user_scatter || p.item_scatter));
+  p.side_fork = p.index == PS_RTM_INDEX_HIST || p.index == PS_RTM_INDEX_FWD_COUNTS;
+  return p;
+}
+extern "C" int ps_rtm_backward_plan(const PsRtmDesc* desc, PsRtmBwdPlan* out) {
+  PS_REQUIRE(desc && out, "rtm backward plan: null argument");
+  RtmWs r; Ws w; PsTemDesc E;
+  TRY(rtm_make_ws(*desc, false, r, w, E));
+  *out = rtm_bwd_plan(*desc, r, ps_deterministic());
+  return PS_OK;
 }
 static int rtm_build_index_hist(const RtmK& k, const RtmWs& r, int V, hipStream_t st) {
   static bool attr = false;
@@ -1907,8 +1971,8 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
   const EncPlan plan = enc_plan(E, T, ws + r.enc_base, w, listed, ws + r.valid);   // what enc_layers_forward will decide
   e.split = make_wsplit(E, T, ws + r.enc_base, w);      // the fused kernels' bf16x3 weight planes ride in this launch
   // the backward's inverted index (rtm_counts_in_forward): its counters are cleared by this launch, filled by the next
-  const bool use_e4 = rtm_embed4_taken(D, k, r);
-  k.count_fwd = rtm_counts_in_forward(D, k, r);
+  const bool use_e4 = rtm_embed4_taken(D, eval, r);
+  k.count_fwd = !eval && rtm_bwd_plan(D, r, k.det != 0).index == PS_RTM_INDEX_FWD_COUNTS;      // (none with a frozen word table)
   if (k.count_fwd) { e.zero_i32 = k.wcnt; e.zero_n = (int)D.vocab_size + 1; }
   if (!eval) e.clear_word = reinterpret_cast<uint32_t*>(ws + r.loss_blk);   // rtm_score_kernel's 64-bit loss word
   TRY(launch_embed_fwd(e, st));
@@ -2046,22 +2110,32 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   hipStream_t st = (hipStream_t)stream;
   fill_k(D, *params, *batch, ws, r, w, false, k);
   const PsRtmTensors& G = *grads;
-  PS_REQUIRE(G.word_emb && (!D.use_seg_emb || G.seg_emb) && G.wo_w && G.wo_b && (k.pvc || G.review_emb),
-             "rtm backward: null gradients");
+  const PsRtmBwdPlan pl = rtm_bwd_plan(D, r, k.det != 0);
+  PS_REQUIRE((!D.use_seg_emb || G.seg_emb) && G.wo_w && G.wo_b, "rtm backward: null gradients");
+  // a NULL table gradient means frozen, and the descriptor says the same (the forward and the plan only see the descriptor)
+  PS_REQUIRE((G.word_emb == nullptr) == ((D.frozen_mask & PS_RTM_FROZEN_WORD) != 0),
+             "rtm backward: the word_emb gradient is %s but frozen_mask = %d", G.word_emb ? "given" : "NULL", D.frozen_mask);
+  PS_REQUIRE(k.pvc || (G.review_emb == nullptr) == ((D.frozen_mask & PS_RTM_FROZEN_REVIEW) != 0),
+             "rtm backward: the review_emb gradient is %s but frozen_mask = %d", G.review_emb ? "given" : "NULL", D.frozen_mask);
+  PS_REQUIRE(!D.use_user_emb || (G.user_emb == nullptr) == ((D.frozen_mask & PS_RTM_FROZEN_USER) != 0),
+             "rtm backward: the user_emb gradient is %s but frozen_mask = %d", G.user_emb ? "given" : "NULL", D.frozen_mask);
+  PS_REQUIRE(!D.use_item_emb || (G.product_emb == nullptr) == ((D.frozen_mask & PS_RTM_FROZEN_ITEM) != 0),
+             "rtm backward: the product_emb gradient is %s but frozen_mask = %d", G.product_emb ? "given" : "NULL", D.frozen_mask);
   k.scale = loss_scale; k.scale_dev = loss_scale_dev;
   k.g_word_emb = G.word_emb; k.g_table = G.review_emb; k.g_seg_emb = G.seg_emb; k.g_wo_w = G.wo_w; k.g_wo_b = G.wo_b;
-  if (D.use_user_emb) { PS_REQUIRE(G.user_emb, "rtm backward: null user_emb gradient"); k.g_user_emb = G.user_emb; }
-  if (D.use_item_emb) { PS_REQUIRE(G.product_emb, "rtm backward: null product_emb gradient"); k.g_item_emb = G.product_emb; }
+  if (pl.user_scatter) k.g_user_emb = G.user_emb;
+  if (pl.item_scatter) k.g_item_emb = G.product_emb;
   const int B = D.B, d = D.d;
-  const bool hist_index = rtm_hist_index(D, k, r);
-  const bool fwd_index = hist_index || rtm_counts_in_forward(D, k, r);     // either way: built on the side stream, right here
+  const bool hist_index = pl.index == PS_RTM_INDEX_HIST;
+  const bool fwd_index = pl.side_fork != 0;     // HIST or FWD_COUNTS — either way: built on the side stream, right here
   if (k.det) {
     // Deterministic mode covers every review encoder (pvc — BASELINE configs[3] —, fs, avg: the word index + ordered reduce; pv:
     // the review rows through the sole-owner row scatter), the user / item embedding rows and the PV loss's word rows.
-    PS_REQUIRE(!k.pvc || hist_index, "rtm backward: deterministic mode needs the LDS-histogram word index (vocabulary <= %d, PS_RTM_HIST != 0)",
+    // (A frozen word table has no index: any vocabulary size.)
+    PS_REQUIRE(!pl.word_reduce || hist_index, "rtm backward: deterministic mode needs the LDS-histogram word index (vocabulary <= %d, PS_RTM_HIST != 0)",
                RTM_HIST_MAXV);
   }
-  k.count_fwd = fwd_index && !hist_index;
+  k.count_fwd = pl.index == PS_RTM_INDEX_FWD_COUNTS;
   if (fwd_index) {    // [count +] allocate + fill on the side stream (or here, without one), under the fused kernel and the attention
     hipStream_t ss = side_stream_or(st);
     if (ss != st) { side_set_light(false); TRY(side_fork(st)); }
@@ -2072,16 +2146,23 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   uint32_t* sig = nullptr; uint32_t sigval = 0;
   static const bool sbwd_carries = ps_diag_int("PS_RTM_SBWD_SIG", 1) != 0;
   if (sbwd_carries) side_take_signal(st, &sig, &sigval);       // the index fill's fork rides on this launch
-  hipLaunchKernelGGL(rtm_score_bwd_kernel, dim3(blocks), dim3(256), (size_t)(d + 1) * sizeof(float), st, k, fwd_index || !k.pvc ? 1 : 0, sig, sigval);
+  // (d query_emb is zeroed by this launch unless the late index's memset below covers it)
+  hipLaunchKernelGGL(rtm_score_bwd_kernel, dim3(blocks), dim3(256), (size_t)(d + 1) * sizeof(float), st, k, pl.index != PS_RTM_INDEX_LATE ? 1 : 0, sig, sigval);
   PS_LAUNCH_CHECK();
   if (k.det) {
     PS_REQUIRE(d <= 512, "rtm backward: deterministic mode supports d <= 512");
     hipLaunchKernelGGL(rtm_score_wo_det_kernel, dim3(1), dim3(256), 0, st, k);
     PS_LAUNCH_CHECK();
   }
-  if (k.train_pv) {
-    hipLaunchKernelGGL(rtm_pv_bwd_kernel, dim3(ps_cdiv(B * k.R, 4)), dim3(256), 0, st, k);
+  if (pl.pv_bwd_kernel) {
+    const dim3 pg(ps_cdiv(B * k.R, 4));
+    const bool wr = (pl.pv_bwd & PS_RTM_PV_WORDS) != 0, dv = (pl.pv_bwd & PS_RTM_PV_DVEC) != 0;
+    if (wr && dv) hipLaunchKernelGGL((rtm_pv_bwd_kernel<true, true>), pg, dim3(256), 0, st, k);
+    else if (dv) hipLaunchKernelGGL((rtm_pv_bwd_kernel<false, true>), pg, dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((rtm_pv_bwd_kernel<true, false>), pg, dim3(256), 0, st, k);
     PS_LAUNCH_CHECK();
+  }
+  if (pl.pv_bwd & PS_RTM_PV_WORDS) {
     if (k.det) {                                     // the PV loss's word rows: sole-owner scatter of ds * vec[review]
       const int ntask = B * k.R * k.W * (k.K + 1);
       float* scr = ps_det_scratch(1, (size_t)3 * ntask + 8, st);
@@ -2100,12 +2181,12 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   ColFoldList fold;
   fold.n = 0;
   // d query_emb (+, when the index is built here, the per-word counters right behind it, rtm_make_ws): one memset
-  if (k.pvc && !fwd_index) {
+  if (pl.index == PS_RTM_INDEX_LATE) {
     const int64_t zend = r.wcnt + (((int64_t)D.vocab_size + 1 + 3) & ~(int64_t)3);
     PS_CHECK_HIP(hipMemsetAsync(ws + r.dqe, 0, sizeof(float) * (size_t)(zend - r.dqe), st));
   }
   const int eb = rtm_slot_blocks(r);
-  if (k.pvc || k.det) k.gs = ws + r.enc_base + w.dx;     // (det + pv encoder: the review rows' gradients are parked in place, scattered below)
+  if (pl.slot_rows) k.gs = ws + r.enc_base + w.dx;     // (det + pv encoder: the review rows' gradients are parked in place, scattered below)
   EncBwdIn in;
   in.fold = &fold; in.rows_listed = rtm_rows_listed(r, w);
   TRY(enc_layers_backward(E, T, TG, nullptr, ws + r.valid, ws + r.enc_base, w, st, in, out));
@@ -2127,13 +2208,19 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
     }
     GemmProblem wg[1] = {gp_wgrad(ws + r.dpre, d, ws + r.raw, d, G.rev_fs_w, d, d, NR)};
     TRY(side_wgrads(wg, 1, st));
-    GemmProblem px = gp(ws + r.dpre, d, 0, params->rev_fs_w, d, 1, ws + r.dmean, d, NR, d, d);
-    TRY(run1(px, st));
-    k.dmean = ws + r.dmean;
+    if (pl.fs_draw) {                              // (frozen words: d raw has no consumer)
+      GemmProblem px = gp(ws + r.dpre, d, 0, params->rev_fs_w, d, 1, ws + r.dmean, d, NR, d, d);
+      TRY(run1(px, st));
+      k.dmean = ws + r.dmean;
+    }
   }
   {
     int npw, nnw;
-    const int nwg = ps_cdiv(rtm_eb_waves(B, D.K, D.R, &npw, &nnw), 4);
+    int nwg = ps_cdiv(rtm_eb_waves(B, D.K, D.R, &npw, &nnw), 4);
+    if (!pl.slot_waves) {                            // frozen form with nothing to feed: the query-position waves alone
+      npw = nnw = 0;
+      nwg = ps_cdiv(ps_cdiv((int64_t)B * (D.K + 1), EB_QSEQ), 4);
+    }
     const FDiv fR = make_fdiv(D.R), fK = make_fdiv(D.K > 0 ? D.K : 1);
     float* sp = ws + r.segpart;
     if (k.det && (k.g_user_emb || k.g_item_emb)) {
@@ -2150,10 +2237,10 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
       if (uk) TRY(launch_rows_scatter_det(uk, npos, dxp, d, d, k.g_user_emb, st));
       if (ik) TRY(launch_rows_scatter_det(ik, npos, dxp, d, d, k.g_item_emb, st));
     }
-    const bool plain = k.pvc && !k.dmean && !k.g_user_emb && !k.g_item_emb && !k.train_pv;
 #define EB_LAUNCH(NK_)                                                                                             \
   do {                                                                                                             \
-    if (plain) hipLaunchKernelGGL((rtm_embed_bwd_kernel<NK_, 1>), dim3(nwg), dim3(256), 0, st, k, sp, npw, nnw, fR, fK); \
+    if (pl.embed_form == PS_RTM_EB_PLAIN) hipLaunchKernelGGL((rtm_embed_bwd_kernel<NK_, 1>), dim3(nwg), dim3(256), 0, st, k, sp, npw, nnw, fR, fK); \
+    else if (pl.embed_form == PS_RTM_EB_FROZEN) hipLaunchKernelGGL((rtm_embed_bwd_kernel<NK_, 2>), dim3(nwg), dim3(256), 0, st, k, sp, npw, nnw, fR, fK); \
     else hipLaunchKernelGGL((rtm_embed_bwd_kernel<NK_, 0>), dim3(nwg), dim3(256), 0, st, k, sp, npw, nnw, fR, fK);       \
   } while (0)
     if (d <= 64) EB_LAUNCH(1);
@@ -2162,7 +2249,7 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
     else EB_LAUNCH(8);
 #undef EB_LAUNCH
     PS_LAUNCH_CHECK();
-    if (k.det && !k.pvc) {                           // pv encoder: the parked review-row gradients -> review_emb, by review id
+    if (k.det && pl.review_scatter) {                // pv encoder: the parked review-row gradients -> review_emb, by review id
       const int npos = r.Bseq * r.S;
       int32_t* rk = reinterpret_cast<int32_t*>(ps_det_scratch(1, (size_t)npos + 8, st));
       PS_REQUIRE(rk, "rtm backward: deterministic mode has no scratch (allocation failed or stream capture)");
@@ -2182,8 +2269,8 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
       f.dst[0] = G.seg_emb; f.dst[1] = G.seg_emb + d; f.dst[2] = G.seg_emb + 2 * (size_t)d;
     }
   }
-  if (k.pvc) {
-    if (!fwd_index) {
+  if (pl.word_reduce) {
+    if (pl.index == PS_RTM_INDEX_LATE) {
       const int V = (int)D.vocab_size;
       TRY(rtm_build_index(k, r, V, true, st));
     }
@@ -2242,8 +2329,10 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
       e.det_dm = ws + r.dqmean;                   // (deterministic mode only: launch_embed_scatter)
     } else {
       TRY(launch_tanh_bwd(ws + r.dqe, d, ws + r.query_emb, ws + r.dqpre, G.fs_b, B, d, st));
-      GemmProblem p = gp(ws + r.dqpre, d, 0, params->fs_w, d, 1, ws + r.dqmean, d, B, d, d);
-      TRY(run1(p, st));
+      if (pl.query_scatter) {                       // (frozen words: d mean has no consumer)
+        GemmProblem p = gp(ws + r.dqpre, d, 0, params->fs_w, d, 1, ws + r.dqmean, d, B, d, d);
+        TRY(run1(p, st));
+      }
       GemmProblem wg[1] = {gp_wgrad(ws + r.dqpre, d, ws + r.qmean, d, G.fs_w, d, d, B)};
       TRY(side_wgrads(wg, 1, st));
       e.dqmean_d = ws + r.dqmean;

@@ -223,6 +223,12 @@ def _refuse_frozen_words(model):
     w = getattr(model, 'word_embeddings', None)
     if w is not None and not w.weight.requires_grad:
         raise NotImplementedError("data-parallel training with a frozen word table (pretrain_emb_dir) is not supported")
+    # the review transformer's other tables (pretrain_emb_dir's doc_emb, fix_emb, pretrain_up_emb_dir): same refusal
+    tabs = getattr(model, '_hot_tables', None)
+    for name, p in (tabs() if tabs is not None else {}).items():
+        if not p.requires_grad:
+            raise NotImplementedError("data-parallel training with a frozen %s table (pretrain_emb_dir / "
+                                      "pretrain_up_emb_dir / fix_emb) is not supported" % name)
 
 
 def flatten_parameters(model, multiple=4):

@@ -26,6 +26,7 @@ from .item_transformer import ItemTransformerRanker
 from .optimizers import build_optim
 from .ps_model import ProductRanker
 from .rtm_loader import ProdSearchDataLoader
+from .rtm_pretrained import PretrainedProductRanker
 
 logger = logging.getLogger('prodsearch_amd')
 
@@ -33,9 +34,13 @@ logger = logging.getLogger('prodsearch_amd')
 def create_model(args, global_data, prod_data, load_path=''):
     """``create_model`` (main.py:141-165)."""
     if args.model_name == 'review_transformer':
-        model = ProductRanker(args, args.device, global_data.vocab_size, global_data.review_count,
-                              global_data.product_size, global_data.user_size, global_data.review_words,
-                              global_data.words, word_dists=prod_data.word_dists)
+        # pretrained / fixed paragraph vectors (ps_model.py:73, 81-86): a directory counts only if it exists
+        pre = getattr(args, 'fix_emb', False) or any(os.path.exists(getattr(args, k, '') or '')
+                                                     for k in ('pretrain_emb_dir', 'pretrain_up_emb_dir'))
+        cls = PretrainedProductRanker if pre else ProductRanker
+        model = cls(args, args.device, global_data.vocab_size, global_data.review_count,
+                    global_data.product_size, global_data.user_size, global_data.review_words,
+                    global_data.words, word_dists=prod_data.word_dists)
     elif args.model_name in ('item_transformer', 'QEM'):
         model = ItemTransformerRanker(args, args.device, global_data.vocab_size, global_data.product_size,
                                       global_data.words, word_dists=prod_data.word_dists)
