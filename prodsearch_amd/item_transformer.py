@@ -27,17 +27,14 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .hot_module import (HotPathModule, _Holder, _Plan, encoder_layer_params, slice_floats,
+                         _LossTensor, _RankLossFn, _check_same_forward)     # noqa: F401  (the last three: importable from here as before)
 
 
 _DET_SET_BY_ARGS = False     # a model's args.deterministic turned the process-wide mode on
 
 
 # ------------------------------------------------------------ parameter holders
-class _Holder(nn.Module):
-    def forward(self, *a, **k):     # pragma: no cover - never on the hot path
-        raise RuntimeError("parameter holder: the hot path runs in libprodsearch_hip.so")
-
-
 class _PositionalEncoding(_Holder):
     """``PositionalEncoding`` buffer (transformer.py:10-19): pe [1, 5000, d]."""
     def __init__(self, dim, max_len=5000):
@@ -107,57 +104,8 @@ def _init_like_reference(module):
             nn.init.normal_(p)
 
 
-# -------------------------------------------------------------------- autograd
-def _check_same_forward(model, step):
-    """Each batch shape owns ONE workspace (activations, sampled negatives, batch pointers) that the next forward
-    overwrites, so only the most recent forward can be differentiated — unlike autograd, which would keep both graphs
-    alive.  Anything else must fail loudly rather than return the other forward's gradients."""
-    if model._fwd_step != step:
-        raise RuntimeError("backward() of a loss whose forward is no longer the model's latest one (forward #%d, now #%d): "
-                           "the HIP workspace holds one forward at a time; call backward() before the next forward()"
-                           % (step, model._fwd_step))
-
-
-class _RankLossFn(torch.autograd.Function):
-    """One node: forward launched the HIP forward; backward launches the HIP backward,
-    which writes the dense ``.grad`` of every reachable parameter directly."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, plan, loss3):
-        ctx.model, ctx.plan, ctx.step = model, plan, model._fwd_step
-        return loss3[0]
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        _check_same_forward(ctx.model, ctx.step)
-        ctx.model._run_backward(ctx.plan, grad_out)
-        return None, None, None, None
-
-
-class _LossTensor(torch.Tensor):
-    """The 0-dim loss ``forward`` returns.  It is an ordinary autograd tensor (``grad_fn`` = the node above), but the
-    trainer's plain ``loss.backward()`` (trainer.py:77) — no ``gradient``, no ``inputs``, no ``create_graph`` — is
-    d loss/d loss = 1 through a single node, so it calls the HIP backward directly: no autograd-engine round trip on
-    the host and no ``ones_like`` fill kernel on the device.  Anything else (scaled losses, retained graphs) takes the
-    normal autograd path."""
-
-    def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
-        fast = self.__dict__.pop('_ps_fast', None)
-        if fast is not None and gradient is None and not create_graph and inputs is None and not retain_graph:
-            model, plan, step = fast
-            _check_same_forward(model, step)         # the workspace must still hold this forward's activations
-            model._run_backward(plan, None)
-            return None
-        return super().backward(gradient, retain_graph, create_graph, inputs)
-
-
-class _Plan(object):
-    """Per-shape cached call state: descriptor, batch struct, workspace."""
-    __slots__ = ('desc', 'batch', 'ws', 'layout', 'key', 'neg_items', 'neg_words', 'keep', 'staged', 'coalesced_at')
-
-
 # ------------------------------------------------------------------------ model
-class ItemTransformerRanker(nn.Module):
+class ItemTransformerRanker(HotPathModule):
     def __init__(self, args, device, vocab_size, product_size, vocab_words, word_dists=None):
         super(ItemTransformerRanker, self).__init__()
         # args.deterministic: bitwise reproducible steps.  The switch is PROCESS-WIDE (ps_set_deterministic); a model built
@@ -242,13 +190,7 @@ class ItemTransformerRanker(nn.Module):
             self._shard.attach(self.product_emb.weight)
             self._shard.init_normal(int(getattr(args, 'seed', 666)))
 
-        self._plans = {}
-        self._params_struct = None
-        self._grads_struct = None
-        self._grad_flat = None
-        self._grad_views = None
-        self._loss_acc = None
-        self._alias = None
+        # (the caches start empty: self.to(device) went through _apply -> _reset_cache)
         self._fwd_step = 0
         self._seed = int(getattr(args, 'seed', 666))
 
@@ -292,9 +234,6 @@ class ItemTransformerRanker(nn.Module):
     def item_loss(self):
         return 0.0 if self._loss_acc is None else float(self._loss_acc[1])
 
-    def load_cp(self, pt, strict=True):
-        self.load_state_dict(pt['model'], strict=strict)
-
     def state_dict(self, *a, **k):
         """With a sharded item table ``product_emb.weight`` is exported as the FULL [P+1, d] table, gathered from the
         ranks' shards (a collective; for catalogue-sized tables export ``model._shard.weight`` per rank instead)."""
@@ -314,12 +253,7 @@ class ItemTransformerRanker(nn.Module):
         return super().load_state_dict(sd, strict=strict, **k)
 
     def forward(self, batch_data, train_pv=False, neg_item_idxs=None, neg_word_idxs=None):
-        plan, loss3 = self._run_forward(batch_data, neg_item_idxs, neg_word_idxs)
-        if not torch.is_grad_enabled():
-            return loss3[0]
-        out = _RankLossFn.apply(self._anchor(), self, plan, loss3).as_subclass(_LossTensor)
-        out._ps_fast = (self, plan, self._fwd_step)
-        return out
+        return self._loss_forward(*self._run_forward(batch_data, neg_item_idxs, neg_word_idxs))
 
     def test(self, batch_data):
         if self.__dict__.get('_shard') is not None:
@@ -359,23 +293,9 @@ class ItemTransformerRanker(nn.Module):
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     # -------------------------------------------------------------------- plumbing
-    def _dev(self):
-        p = self.word_embeddings.weight
-        if not p.is_cuda:
-            raise RuntimeError("ItemTransformerRanker needs its parameters on a gfx950 device "
-                               "(no CPU fallback): model.to('cuda')")
-        return p.device
+    _TENSORS = _lib.PsTemTensors
 
-    def _anchor(self):
-        a = getattr(self, '_anchor_t', None)
-        if a is None or a.device != self._dev():
-            a = torch.zeros((), device=self._dev(), requires_grad=True)
-            self._anchor_t = a
-        return a
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        # storage may have moved: drop cached pointers
+    def _reset_cache(self):
         self._plans = {}
         self._params_struct = None
         self._grads_struct = None
@@ -387,7 +307,6 @@ class ItemTransformerRanker(nn.Module):
         self.__dict__.pop('_param_flat', None)
         if self.__dict__.get('_shard') is not None and self.product_emb.weight.device == self._shard.device:
             self._shard.attach(self.product_emb.weight)          # the receive buffer moved with the parameter
-        return r
 
     def _named_hot_params(self):
         """(C-ABI field path, parameter) of every tensor the kernels read."""
@@ -403,16 +322,7 @@ class ItemTransformerRanker(nn.Module):
         if a.model_name == 'item_transformer':
             te = self.transformer_encoder
             out += [(('final_ln_g',), te.layer_norm.weight), (('final_ln_b',), te.layer_norm.bias)]
-            for i, l in enumerate(te.transformer_inter):
-                sa, ff = l.self_attn, l.feed_forward
-                out += [(('layer', i, 'wk'), sa.linear_keys.weight), (('layer', i, 'bk'), sa.linear_keys.bias),
-                        (('layer', i, 'wv'), sa.linear_values.weight), (('layer', i, 'bv'), sa.linear_values.bias),
-                        (('layer', i, 'wq'), sa.linear_query.weight), (('layer', i, 'bq'), sa.linear_query.bias),
-                        (('layer', i, 'wo'), sa.final_linear.weight), (('layer', i, 'bo'), sa.final_linear.bias),
-                        (('layer', i, 'w1'), ff.w_1.weight), (('layer', i, 'b1'), ff.w_1.bias),
-                        (('layer', i, 'w2'), ff.w_2.weight), (('layer', i, 'b2'), ff.w_2.bias),
-                        (('layer', i, 'ff_ln_g'), ff.layer_norm.weight), (('layer', i, 'ff_ln_b'), ff.layer_norm.bias),
-                        (('layer', i, 'ln_g'), l.layer_norm.weight), (('layer', i, 'ln_b'), l.layer_norm.bias)]
+            out += encoder_layer_params(te)
         return out
 
     def _has_grad(self, path):
@@ -427,78 +337,37 @@ class ItemTransformerRanker(nn.Module):
             return path[1] != 0
         return True
 
-    @staticmethod
-    def _set_field(struct, path, value):
-        if path[0] == 'layer':
-            setattr(struct.layer[path[1]], path[2], value)
-        else:
-            setattr(struct, path[0], value)
+    def _grad_key(self):
+        return self.word_embeddings.weight.requires_grad
 
-    def _structs(self):
-        if self._params_struct is not None:
-            if self.__dict__.get('_word_grad_at') == self.word_embeddings.weight.requires_grad:
-                return self._params_struct, self._grads_struct
-            self._regrade()
-        dev = self._dev()
-        hot = self._named_hot_params()
-        for _, p in hot:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("parameters must be contiguous fp32")
-        ps, gs = _lib.PsTemTensors(), _lib.PsTemTensors()
-        for path, p in hot:
-            self._set_field(ps, path, p.data_ptr())
+    def _grad_order(self, path, p):
+        """Small dense tensors, [the sharded table's receive buffer], row-sparse tables; by size within each."""
+        return (path in self._sparse_paths(), self._shard is not None and path == ('product_emb',), p.numel())
+
+    def _fill_extra(self, ps):
         if self.args.model_name == 'item_transformer':
             ps.pe = self.transformer_encoder.pos_emb.pe.data_ptr()
-        # one flat gradient buffer: small tensors first, tables last; 16-byte aligned slices
-        graded = [(path, p) for path, p in hot if self._has_grad(path)]
+
+    def _structs_built(self, graded):
         sparse = self._sparse_paths()
-        # order: small dense tensors, [the sharded table's receive buffer], row-sparse tables
-        graded.sort(key=lambda t: (t[0] in sparse, self._shard is not None and t[0] == ('product_emb',), t[1].numel()))
-        offs, cur = [], 0
-        for _, p in graded:
-            offs.append(cur)
-            cur += (p.numel() + 3) // 4 * 4
-        pad = int(self.__dict__.get('_flat_pad_to', 4))       # dist.flatten_parameters: a multiple of 4 * world
-        cur = (cur + pad - 1) // pad * pad
-        self._grad_flat = torch.zeros(cur, device=dev, dtype=torch.float32)
-        self._grad_views = []
-        for (path, p), o in zip(graded, offs):
-            v = self._grad_flat[o:o + p.numel()].view_as(p)
-            self._grad_views.append((p, v))
-            self._set_field(gs, path, v.data_ptr())
-        self._n_small = sum((p.numel() + 3) // 4 * 4 for _, p in graded if p.numel() < (1 << 20))
+        self._n_small = sum(slice_floats(p.numel()) for _, p, _ in graded if p.numel() < (1 << 20))
         # row-sparse mode: the flat buffer is [dense tensors | row-sparse tables]; only the first part is
         # ever memset, table rows are re-zeroed by the optimizer (or zero_grad) through their touched list
-        self._n_dense_grad = sum((p.numel() + 3) // 4 * 4 for path, p in graded if path not in sparse)
+        self._n_dense_grad = sum(slice_floats(p.numel()) for path, p, _ in graded if path not in sparse)
         # what a data-parallel exchange all-reduces: the small tensors only — with a sharded item table the receive buffer's
         # gradient (the LARGEST of the non-sparse tensors, hence the last of them) travels to the owners instead
-        self._n_allreduce_grad = self._n_dense_grad - ((self.product_emb.weight.numel() + 3) // 4 * 4 if self._shard is not None else 0)
-        self._sparse_tabs = [(path, p, v) for (path, p), (_, v) in zip(graded, self._grad_views) if path in sparse]
-        self._params_struct, self._grads_struct = ps, gs
-        self.__dict__['_word_grad_at'] = self.word_embeddings.weight.requires_grad
-        self._loss_acc = torch.zeros(2, device=dev, dtype=torch.float32)
-        return ps, gs
+        self._n_allreduce_grad = self._n_dense_grad - (slice_floats(self.product_emb.weight.numel()) if self._shard is not None else 0)
+        self._sparse_tabs = [t for t in graded if t[0] in sparse]
+        self._loss_acc = torch.zeros(2, device=self._dev(), dtype=torch.float32)
 
-    def _regrade(self):
-        """``word_embeddings.weight.requires_grad`` changed since the structs were built: the gradient struct, the flat
-        gradient buffer and its views are rebuilt by the caller (_structs), so a frozen table never receives a gradient and a
-        trainable one never loses it.  The gradients of the previous layout are dropped (``.grad = None``, as after
-        ``zero_grad()``); the optimizer re-plans on the new ``.grad`` tensors, keeping its moments, and a graph-replayed backward is captured again (its key holds the gradient pointers).  The
-        data-parallel forms (flat parameter buffer) and lazy_exact_adam (rows replayed against the table's history) refuse."""
+    def _regrade_refusal(self):
+        """``word_embeddings.weight.requires_grad`` changed after the first step.  A graph-replayed backward is simply captured
+        again (its key holds the gradient pointers); the data-parallel forms (flat parameter buffer) and lazy_exact_adam (rows
+        replayed against the table's history) refuse."""
         if self.__dict__.get('_param_flat') is not None or self._lazy_exact():
-            raise RuntimeError("word_embeddings.weight.requires_grad changed after the first step: not supported with %s"
-                               % ("lazy_exact_adam" if self._lazy_exact() else "a data-parallel exchange"))
-        for p, v in self._grad_views or ():
-            if p.grad is not None:
-                if p.grad is not v and p.grad.data_ptr() != v.data_ptr():
-                    raise RuntimeError("a foreign .grad tensor is attached to a hot-path parameter; "
-                                       "call model.zero_grad() before backward")
-                p.grad = None
-        self.__dict__['_grad_clean'] = False
-        self._params_struct = None
-        self._grads_struct = None
-        self._grad_flat = None
-        self._grad_views = None
+            return ("word_embeddings.weight.requires_grad changed after the first step: not supported with %s"
+                    % ("lazy_exact_adam" if self._lazy_exact() else "a data-parallel exchange"))
+        return None
 
     def _check_idx(self, t, name, shape_tail=None):
         if not torch.is_tensor(t) or t.dtype != torch.int64 or not t.is_cuda:
@@ -577,24 +446,6 @@ class ItemTransformerRanker(nn.Module):
                 b.neg_item_idxs = b.neg_word_idxs = None
                 keep += [tg, pw]
         plan.keep = keep       # keep the index tensors alive until backward has run
-
-    def _stream(self):
-        return torch.cuda.current_stream(self._dev()).cuda_stream
-
-    def _alias_tables(self):
-        if self._alias is None:
-            if self.word_dists is None:
-                raise RuntimeError("word_dists is required to sample negative words "
-                                   "(or pass neg_word_idxs= explicitly)")
-            lib = _lib.load()
-            wd = self.word_dists.contiguous()
-            n = wd.numel()
-            prob = torch.empty(n, dtype=torch.float32)
-            alias = torch.empty(n, dtype=torch.int32)
-            _lib.check(lib.ps_build_alias_host(wd.data_ptr(), n, prob.data_ptr(), alias.data_ptr()),
-                       'ps_build_alias_host')
-            self._alias = (prob.to(self._dev()), alias.to(self._dev()))
-        return self._alias
 
     def sample_negatives(self, plan):
         """The two ``torch.multinomial`` draws (item_transformer.py:447, :268) on the device."""
@@ -841,11 +692,10 @@ class ItemTransformerRanker(nn.Module):
                                        if flag == 1 else "touched-row list of %s overflowed its capacity" % name))
 
     def _zero_for_backward(self):
+        if not self._row_sparse():
+            return super()._zero_for_backward()
         lib = _lib.load()
         st = self._stream()
-        if not self._row_sparse():
-            _lib.check(lib.ps_zero_floats(self._grad_flat.data_ptr(), self._grad_flat.numel(), st), 'ps_zero_floats')
-            return
         _lib.check(lib.ps_zero_floats(self._grad_flat.data_ptr(), self._n_dense_grad, st), 'ps_zero_floats')
         for path, p, gview in self._sparse_tabs:
             info = getattr(p, '_ps_rows', None)
@@ -866,18 +716,6 @@ class ItemTransformerRanker(nn.Module):
             plist = self.__dict__['_zg_params'] = list(self.parameters())
         for p in plist:
             p.grad = None
-
-    def _assign_grads(self):
-        """Give every reachable parameter its dense ``.grad`` view; returns True if the flat
-        buffer must be zeroed first (i.e. zero_grad() ran, trainer.py:76)."""
-        fresh = self._grad_views[0][0].grad is None
-        for p, v in self._grad_views:
-            if p.grad is None:
-                p.grad = v
-            elif p.grad.data_ptr() != v.data_ptr():
-                raise RuntimeError("a foreign .grad tensor is attached to a hot-path parameter; "
-                                   "call model.zero_grad() before backward")
-        return fresh
 
     def _run_backward(self, plan, grad_out):
         lib = _lib.load()
@@ -962,12 +800,3 @@ class ItemTransformerRanker(nn.Module):
         _lib.check(lib.ps_tem_score(d, ps, plan.batch, plan.ws.data_ptr(), scores.data_ptr(), self._stream()),
                    'ps_tem_score')
         return scores
-
-    # --------------------------------------------------------------- test support
-    def workspace_view(self, plan, name, shape):
-        """View of one intermediate inside the workspace (parity tests compare every stage)."""
-        off = getattr(plan.layout, name)
-        n = 1
-        for s in shape:
-            n *= s
-        return plan.ws[off:off + n].view(*shape)

@@ -25,7 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .item_transformer import _FSEncoder, _Holder, _TransformerEncoder, _init_like_reference
+from .hot_module import HotPathModule, _Holder, _Plan, encoder_layer_params
+from .item_transformer import _FSEncoder, _TransformerEncoder, _init_like_reference
 
 
 class _ReviewEncoder(_Holder):
@@ -40,21 +41,7 @@ class _ReviewEncoder(_Holder):
             self.context_embeddings = word_embeddings
 
 
-class _RtmLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, anchor, model, plan, loss3):
-        ctx.model, ctx.plan, ctx.step = model, plan, model._fwd_step
-        return loss3[0]
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        from .item_transformer import _check_same_forward
-        _check_same_forward(ctx.model, ctx.step)
-        ctx.model._run_backward(ctx.plan, grad_out)
-        return None, None, None, None
-
-
-class ProductRanker(nn.Module):
+class ProductRanker(HotPathModule):
     def __init__(self, args, device, vocab_size, review_count, product_size, user_size,
                  review_words, vocab_words, word_dists=None):
         super(ProductRanker, self).__init__()
@@ -147,9 +134,6 @@ class ProductRanker(nn.Module):
             _init_like_reference(self.query_encoder)
         _init_like_reference(self.transformer_encoder)
 
-    def load_cp(self, pt, strict=True):
-        self.load_state_dict(pt['model'], strict=strict)
-
     def clear_review_embbeddings(self):           # (sic) reference spelling, ps_model.py:177
         if not self.fix_emb:                      # fix_emb: the table is the frozen parameter and stays (:179)
             self.review_embeddings = None
@@ -175,47 +159,19 @@ class ProductRanker(nn.Module):
         self.review_embeddings = out
 
     def forward(self, batch_data, train_pv=True, neg_word_idxs=None):
-        plan, loss3 = self._run_forward(batch_data, bool(train_pv), neg_word_idxs)
-        if not torch.is_grad_enabled():
-            return loss3[0]
-        # same direct path as ItemTransformerRanker: a plain ``loss.backward()`` calls the HIP backward without the
-        # autograd engine's round trip and its ``ones_like`` fill kernel (item_transformer._LossTensor)
-        from .item_transformer import _LossTensor
-        out = _RtmLossFn.apply(self._anchor(), self, plan, loss3).as_subclass(_LossTensor)
-        out._ps_fast = (self, plan, self._fwd_step)
-        return out
+        return self._loss_forward(*self._run_forward(batch_data, bool(train_pv), neg_word_idxs))
 
     def test(self, batch_data):
         return self._run_score(batch_data)
 
     # -------------------------------------------------------------------- plumbing
+    _TENSORS = _lib.PsRtmTensors
+
     def _reset_cache(self):
         self._plans = {}
         self._params_struct = self._grads_struct = None
         self._grad_flat = self._grad_views = None
         self._alias = None
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._reset_cache()
-        return r
-
-    def _dev(self):
-        p = self.word_embeddings.weight
-        if not p.is_cuda:
-            raise RuntimeError("ProductRanker needs its parameters on a gfx950 device (no CPU fallback): "
-                               "model.to('cuda')")
-        return p.device
-
-    def _stream(self):
-        return torch.cuda.current_stream(self._dev()).cuda_stream
-
-    def _anchor(self):
-        a = getattr(self, '_anchor_t', None)
-        if a is None or a.device != self._dev():
-            a = torch.zeros((), device=self._dev(), requires_grad=True)
-            self._anchor_t = a
-        return a
 
     def _named_hot_params(self):
         a, te = self.args, self.transformer_encoder
@@ -232,16 +188,7 @@ class ProductRanker(nn.Module):
             out.append((('product_emb',), self.product_emb.weight))
         if a.query_encoder_name == 'fs':
             out += [(('fs_w',), self.query_encoder.f_W.weight), (('fs_b',), self.query_encoder.f_W.bias)]
-        for i, l in enumerate(te.transformer_inter):
-            sa, ff = l.self_attn, l.feed_forward
-            out += [(('layer', i, 'wk'), sa.linear_keys.weight), (('layer', i, 'bk'), sa.linear_keys.bias),
-                    (('layer', i, 'wv'), sa.linear_values.weight), (('layer', i, 'bv'), sa.linear_values.bias),
-                    (('layer', i, 'wq'), sa.linear_query.weight), (('layer', i, 'bq'), sa.linear_query.bias),
-                    (('layer', i, 'wo'), sa.final_linear.weight), (('layer', i, 'bo'), sa.final_linear.bias),
-                    (('layer', i, 'w1'), ff.w_1.weight), (('layer', i, 'b1'), ff.w_1.bias),
-                    (('layer', i, 'w2'), ff.w_2.weight), (('layer', i, 'b2'), ff.w_2.bias),
-                    (('layer', i, 'ff_ln_g'), ff.layer_norm.weight), (('layer', i, 'ff_ln_b'), ff.layer_norm.bias),
-                    (('layer', i, 'ln_g'), l.layer_norm.weight), (('layer', i, 'ln_b'), l.layer_norm.bias)]
+        out += encoder_layer_params(te)
         return out
 
     _TABLE_BITS = (('word_emb', _lib.PS_RTM_FROZEN_WORD), ('review_emb', _lib.PS_RTM_FROZEN_REVIEW),
@@ -271,63 +218,23 @@ class ProductRanker(nn.Module):
             return path[1] != 0
         return True
 
-    @staticmethod
-    def _set_field(struct, path, value):
-        if path[0] == 'layer':
-            setattr(struct.layer[path[1]], path[2], value)
-        else:
-            setattr(struct, path[0], value)
+    def _grad_key(self):
+        return self._frozen_mask()      # one mask over at most four parameters per call
 
-    def _structs(self):
-        if self._params_struct is not None:
-            if self.__dict__.get('_frozen_at') == self._frozen_mask():
-                return self._params_struct, self._grads_struct
-            self._regrade()
-        dev = self._dev()
-        hot = self._named_hot_params()
-        ps, gs = _lib.PsRtmTensors(), _lib.PsRtmTensors()
-        for path, p in hot:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("parameters must be contiguous fp32")
-            self._set_field(ps, path, p.data_ptr())
+    def _fill_extra(self, ps):
         ps.pe = self.transformer_encoder.pos_emb.pe.data_ptr()
-        graded = [(path, p) for path, p in hot if self._has_grad(path)]
-        graded.sort(key=lambda t: t[1].numel())
-        offs, cur = [], 0
-        for _, p in graded:
-            offs.append(cur)
-            cur += (p.numel() + 3) // 4 * 4
-        pad = int(self.__dict__.get('_flat_pad_to', 4))       # dist.flatten_parameters: a multiple of 4 * world
-        cur = (cur + pad - 1) // pad * pad
-        self._grad_flat = torch.zeros(cur, device=dev, dtype=torch.float32)
-        self._grad_views = []
-        for (path, p), o in zip(graded, offs):
-            v = self._grad_flat[o:o + p.numel()].view_as(p)
-            self._grad_views.append((p, v))
-            self._set_field(gs, path, v.data_ptr())
-        self._params_struct, self._grads_struct = ps, gs
-        self.__dict__['_frozen_at'] = self._frozen_mask()
-        return ps, gs
 
-    def _regrade(self):
-        """``requires_grad`` of a hot table changed since the structs were built: the gradient struct, the flat gradient
-        buffer and its views are rebuilt by the caller (_structs), as ItemTransformerRanker does for its word table.  The
-        gradients of the previous layout are dropped (``.grad = None``, as after ``zero_grad()``); the optimizer re-plans on
-        the new ``.grad`` tensors, keeping its moments.  The cached descriptors carry the frozen mask and are dropped too.
-        The check is one mask over at most four parameters per call.  A flip BETWEEN a forward and its backward is not
-        supported: the backward then holds the forward's descriptor with the old mask beside the rebuilt gradient struct,
-        and ``ps_rtm_backward`` refuses the pair (its frozen_mask message) before launching anything."""
+    def _regrade_refusal(self):
         if self.__dict__.get('_param_flat') is not None:
-            raise RuntimeError("requires_grad of an embedding table changed after the first step: not supported with a "
-                               "data-parallel exchange")
-        for p, v in self._grad_views or ():
-            if p.grad is not None:
-                if p.grad is not v and p.grad.data_ptr() != v.data_ptr():
-                    raise RuntimeError("a foreign .grad tensor is attached to a hot-path parameter; "
-                                       "call model.zero_grad() before backward")
-                p.grad = None
-        self.__dict__['_grad_clean'] = False
-        self._params_struct = self._grads_struct = None
+            return ("requires_grad of an embedding table changed after the first step: not supported with a "
+                    "data-parallel exchange")
+        return None
+
+    def _regraded(self):
+        """The cached descriptors carry the frozen mask and are dropped with the old gradient layout.  A flip BETWEEN a
+        forward and its backward is not supported: the backward then holds the forward's descriptor with the old mask beside
+        the rebuilt gradient struct, and ``ps_rtm_backward`` refuses the pair (its frozen_mask message) before launching
+        anything."""
         self._plans = {}
 
     def _desc(self, B, K, R, eval_mode, C=0, Q=1, W=1, WL=0, train_pv=False):
@@ -385,29 +292,19 @@ class ProductRanker(nn.Module):
             _lib.check(lib.ps_rtm_workspace_floats(desc, int(eval_mode), C.byref(tot)), 'ps_rtm_workspace_floats')
             lay = _lib.PsRtmWsLayout()
             _lib.check(lib.ps_rtm_workspace_layout(desc, int(eval_mode), lay), 'ps_rtm_workspace_layout')
-            plan = dict(desc=desc, batch=_lib.PsRtmBatch(), ws=torch.empty(tot.value, device=self._dev(), dtype=torch.float32),
-                        neg_words=None, keep=None, layout=lay)
+            plan = _Plan()
+            plan.key, plan.desc, plan.layout, plan.batch = key, desc, lay, _lib.PsRtmBatch()
+            plan.ws = torch.empty(tot.value, device=self._dev(), dtype=torch.float32)
+            plan.neg_words = plan.keep = None
             self._plans[key] = plan
         return plan
-
-    def _alias_tables(self):
-        if self._alias is None:
-            if self.word_dists is None:
-                raise RuntimeError("word_dists is required to sample the PV-loss words (or pass neg_word_idxs=)")
-            lib = _lib.load()
-            wd = self.word_dists.contiguous()
-            n = wd.numel()
-            prob, alias = torch.empty(n, dtype=torch.float32), torch.empty(n, dtype=torch.int32)
-            _lib.check(lib.ps_build_alias_host(wd.data_ptr(), n, prob.data_ptr(), alias.data_ptr()), 'ps_build_alias_host')
-            self._alias = (prob.to(self._dev()), alias.to(self._dev()))
-        return self._alias
 
     def _sample_pv_words(self, plan, n_rev, W, K):
         """``torch.multinomial(word_dists, B*R*W*K)`` (PV.py:57 / PVC.py:81) on the device."""
         lib = _lib.load()
-        if plan['neg_words'] is None:
-            plan['neg_words'] = torch.empty(n_rev, W * K, device=self._dev(), dtype=torch.int64)
-            plan['dummy_items'] = torch.empty(1, device=self._dev(), dtype=torch.int64)
+        if plan.neg_words is None:
+            plan.neg_words = torch.empty(n_rev, W * K, device=self._dev(), dtype=torch.int64)
+            plan.dummy_items = torch.empty(1, device=self._dev(), dtype=torch.int64)
         sd = _lib.PsTemDesc()
         sd.B, sd.K, sd.W = n_rev, K, W
         sd.product_size, sd.vocab_size = 1, self.vocab_size
@@ -416,8 +313,8 @@ class ProductRanker(nn.Module):
         # item draws are not needed here: ask for zero of them by sampling only the word stream (B*W*K words)
         items = torch.empty(n_rev * K, device=self._dev(), dtype=torch.int64)
         _lib.check(lib.ps_sample_negatives(sd, prob.data_ptr(), alias.data_ptr(), items.data_ptr(),
-                                           plan['neg_words'].data_ptr(), self._stream()), 'ps_sample_negatives')
-        return plan['neg_words']
+                                           plan.neg_words.data_ptr(), self._stream()), 'ps_sample_negatives')
+        return plan.neg_words
 
     _POS_SEQ = (('pos_prod_ridxs', 1, 'review'), ('pos_seg_idxs', 1, 'seg'), ('pos_user_idxs', 1, 'user'),
                 ('pos_item_idxs', 1, 'item'), ('pos_prod_rword_idxs', 1, 'word3'), ('pos_prod_rword_masks', 1, 'mask3'),
@@ -475,8 +372,8 @@ class ProductRanker(nn.Module):
         desc = self._desc(B, K, R, False, 0, Q, W, WL, train_pv)
         plan = self._plan(key, desc, False)
         self._fwd_step += 1
-        plan['desc'].step = self._fwd_step
-        bt = plan['batch']
+        plan.desc.step = self._fwd_step
+        bt = plan.batch
         keep = [qw, pr, nr, pw]
         bt.query_word_idxs, bt.pos_prod_ridxs, bt.neg_prod_ridxs = qw.data_ptr(), pr.data_ptr(), nr.data_ptr()
         bt.pos_prod_rword_idxs = pw.data_ptr()
@@ -502,9 +399,9 @@ class ProductRanker(nn.Module):
         self._seq_ids(bt, b, ('pos_user_idxs', 'neg_user_idxs', 'pos_item_idxs', 'neg_item_idxs'),
                       dict(pos_user_idxs=(B, R + 1), pos_item_idxs=(B, R + 1),
                            neg_user_idxs=(B, K, R + 1), neg_item_idxs=(B, K, R + 1)), keep)
-        plan['keep'] = keep
+        plan.keep = keep
         loss3 = torch.empty(3, device=self._dev(), dtype=torch.float32)
-        _lib.check(lib.ps_rtm_forward(plan['desc'], ps, bt, plan['ws'].data_ptr(), loss3.data_ptr(), self._stream()),
+        _lib.check(lib.ps_rtm_forward(plan.desc, ps, bt, plan.ws.data_ptr(), loss3.data_ptr(), self._stream()),
                    'ps_rtm_forward')
         return plan, loss3
 
@@ -512,17 +409,11 @@ class ProductRanker(nn.Module):
         lib = _lib.load()
         ps, gs = self._structs()
         st = self._stream()
-        fresh = self._grad_views[0][0].grad is None
-        for p, v in self._grad_views:
-            if p.grad is None:
-                p.grad = v
-            elif p.grad.data_ptr() != v.data_ptr():
-                raise RuntimeError("a foreign .grad tensor is attached; call model.zero_grad() before backward")
-        if fresh and not self.__dict__.get('_grad_clean', False):     # (clean: the last optimizer step left the buffer at 0)
-            _lib.check(lib.ps_zero_floats(self._grad_flat.data_ptr(), self._grad_flat.numel(), st), 'ps_zero_floats')
+        if self._assign_grads() and not self.__dict__.get('_grad_clean', False):     # (clean: the last optimizer step left the buffer at 0)
+            self._zero_for_backward()
         self.__dict__['_grad_clean'] = False
         go = None if grad_out is None else grad_out.contiguous().float()          # None: d loss / d loss = 1
-        _lib.check(lib.ps_rtm_backward(plan['desc'], ps, plan['batch'], plan['ws'].data_ptr(), gs, 1.0,
+        _lib.check(lib.ps_rtm_backward(plan.desc, ps, plan.batch, plan.ws.data_ptr(), gs, 1.0,
                                        None if go is None else go.data_ptr(), st), 'ps_rtm_backward')
 
     def _run_score(self, batch):
@@ -537,24 +428,15 @@ class ProductRanker(nn.Module):
         key = ('eval', B, C, R, qw.shape[1])
         desc = self._desc(B, 0, R, True, C, qw.shape[1], 1, int(self.review_words.shape[1]))
         plan = self._plan(key, desc, True)
-        bt = plan['batch']
+        bt = plan.batch
         tab = self.review_embeddings.detach().contiguous()
         bt.query_word_idxs, bt.candi_prod_ridxs, bt.candi_seg_idxs = qw.data_ptr(), cr.data_ptr(), cs.data_ptr()
         bt.review_embeddings = tab.data_ptr()
         keep = [qw, cr, cs, tab]
         self._seq_ids(bt, batch, ('candi_seq_user_idxs', 'candi_seq_item_idxs'),
                       dict(candi_seq_user_idxs=(B, C, R + 1), candi_seq_item_idxs=(B, C, R + 1)), keep)
-        plan['keep'] = keep
+        plan.keep = keep
         scores = torch.empty(B, C, device=self._dev(), dtype=torch.float32)
-        _lib.check(lib.ps_rtm_score(plan['desc'], ps, bt, plan['ws'].data_ptr(), scores.data_ptr(), self._stream()),
+        _lib.check(lib.ps_rtm_score(plan.desc, ps, bt, plan.ws.data_ptr(), scores.data_ptr(), self._stream()),
                    'ps_rtm_score')
         return scores
-
-    # --------------------------------------------------------------- test support
-    def workspace_view(self, plan, name, shape):
-        """View of one intermediate inside the workspace (parity tests compare every stage; PsRtmWsLayout)."""
-        off = getattr(plan['layout'], name)
-        n = 1
-        for s in shape:
-            n *= s
-        return plan['ws'][off:off + n].view(*shape)

@@ -10,6 +10,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from prodsearch_amd import dist as pdist
+from prodsearch_amd.hot_module import flat_layout
 
 
 def _free_port():
@@ -165,13 +166,8 @@ class _StubModel(torch.nn.Module):
         if self._params_struct is not None:
             return self._params_struct, self._grads_struct
         graded = sorted(self._named_hot_params(), key=lambda t: t[1].numel())
-        offs, cur = [], 0
-        for _, p in graded:
-            offs.append(cur)
-            cur += (p.numel() + 3) // 4 * 4
-        pad = int(self.__dict__.get('_flat_pad_to', 4))
-        cur = (cur + pad - 1) // pad * pad
-        self._grad_flat = torch.zeros(cur)
+        offs, total = flat_layout([p.numel() for _, p in graded], int(self.__dict__.get('_flat_pad_to', 4)))
+        self._grad_flat = torch.zeros(total)
         self._grad_views = [(p, self._grad_flat[o:o + p.numel()].view_as(p)) for (_, p), o in zip(graded, offs)]
         self._params_struct, self._grads_struct = {}, {}
         return self._params_struct, self._grads_struct

@@ -216,7 +216,7 @@ def _plan_of(m):
     from prodsearch_amd import _lib
     plan = [p for k, p in m._plans.items() if k[0] != 'eval'][-1]
     out = _lib.PsRtmBwdPlan()
-    _lib.check(_lib.load().ps_rtm_backward_plan(C.byref(plan['desc']), C.byref(out)), 'ps_rtm_backward_plan')
+    _lib.check(_lib.load().ps_rtm_backward_plan(C.byref(plan.desc), C.byref(out)), 'ps_rtm_backward_plan')
     return out
 
 
@@ -443,12 +443,12 @@ def test_backward_refuses_gradient_pointers_that_disagree_with_the_mask():
     bt, _ = _batch(a, rw, wd, 60, 4, False)
     plan, loss3 = m._run_forward(bt.to('cuda'), False)
     ps, gs = m._structs()
-    desc = plan['desc']
+    desc = plan.desc
     desc.frozen_mask = 0                                                         # ... but the word gradient is NULL
-    rc = _lib.load().ps_rtm_backward(desc, ps, plan['batch'], plan['ws'].data_ptr(), gs, 1.0, None, m._stream())
+    rc = _lib.load().ps_rtm_backward(desc, ps, plan.batch, plan.ws.data_ptr(), gs, 1.0, None, m._stream())
     assert rc != 0 and b'frozen_mask' in _lib.load().ps_last_error()
     desc.frozen_mask = _lib.PS_RTM_FROZEN_WORD
-    _lib.check(_lib.load().ps_rtm_backward(desc, ps, plan['batch'], plan['ws'].data_ptr(), gs, 1.0, None, m._stream()),
+    _lib.check(_lib.load().ps_rtm_backward(desc, ps, plan.batch, plan.ws.data_ptr(), gs, 1.0, None, m._stream()),
                'ps_rtm_backward')
     torch.cuda.synchronize()
 

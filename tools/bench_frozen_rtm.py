@@ -84,7 +84,7 @@ def timed(step, steps):
 def plan_line(m):
     plan = [p for k, p in m._plans.items() if k[0] != 'eval'][-1]
     out = _lib.PsRtmBwdPlan()
-    _lib.check(_lib.load().ps_rtm_backward_plan(C.byref(plan['desc']), C.byref(out)), 'ps_rtm_backward_plan')
+    _lib.check(_lib.load().ps_rtm_backward_plan(C.byref(plan.desc), C.byref(out)), 'ps_rtm_backward_plan')
     return ' '.join('%s=%d' % (n, getattr(out, n)) for n, _ in out._fields_)
 
 
