@@ -20,6 +20,7 @@
 // fan-in, d ctx = dhalf Wo, the attention backward (one workgroup per batch row), deterministic bias column sums, the weight
 // gradients and the d h / d query products, then the history-row scatter into the table.
 #include "encoder.h"
+#include "wgrad.h"
 #include <string.h>
 
 #define AE_THREADS 256
@@ -326,7 +327,7 @@ int ae_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G
     GemmProblem p = gp(dhalf, d, 0, A.wo, d, 1, ws + w.dctx, d, B * R, d, d);
     TRY(run1(p, st));
     GemmProblem g = gp_wgrad(dhalf, d, ws + l.ctx, d, GA.wo, d, d, B * R);
-    TRY(main_wgrads(&g, 1, st));
+    TRY(run_wgrads(&g, 1, st));
   }
   AeAttnArgs a = ae_args(D, ui, ws, w);
   a.dctx = ws + w.dctx; a.dk = ws + w.ae_dk; a.dv = ws + w.ae_dv; a.dqp = ws + w.ae_dqp;
@@ -350,9 +351,9 @@ int ae_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G
   }
   {   // dWk += dK^T h, dWv += dV^T h (one launch), dWq += dQ^T query_emb
     GemmProblem g[2] = {gp_wgrad(a.dk, d, ws + w.x, d, GA.wk, d, d, B * S), gp_wgrad(a.dv, d, ws + w.x, d, GA.wv, d, d, B * S)};
-    TRY(main_wgrads(g, 2, st));
+    TRY(run_wgrads(g, 2, st));
     GemmProblem gq = gp_wgrad(a.dqp, d, ws + w.query_emb, d, GA.wq, d, d, B);
-    TRY(main_wgrads(&gq, 1, st));
+    TRY(run_wgrads(&gq, 1, st));
   }
   {   // d h = dK . Wk + dV . Wv ; d query_emb += dQ . Wq
     GemmProblem p1 = gp(a.dk, d, 0, A.wk, d, 1, ws + w.dx, d, B * S, d, d);

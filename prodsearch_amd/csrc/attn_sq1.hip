@@ -9,6 +9,7 @@
 // Everything is LDS-resident fp32 VALU work (S <= 64, a few KB per sequence); replicas are
 // processed in chunks of JC so that the Philox masks are generated once per element.
 #include "rowwise.h"
+#include "side_stream.h"
 #include "x3frag.h"
 #include <stdlib.h>
 

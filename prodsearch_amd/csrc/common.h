@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/prodsearch_hip.h"
 
 #define PS_WAVE 64
@@ -25,6 +26,7 @@ void ps_set_error(const char* fmt, ...);
     }                                                                             \
   } while (0)
 #define PS_LAUNCH_CHECK() PS_CHECK_HIP(hipGetLastError())
+#define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
 static inline int ps_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
@@ -35,7 +37,6 @@ static inline int ps_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b);
 // (hipcc -DPS_DIAG: `python -m prodsearch_amd.build --diag` -> lib/libprodsearch_hip_diag.so, which prodsearch_amd._lib
 // loads when PS_DIAG_LIB=1); in the shipped library the call folds to its default and a stray variable in a training
 // environment changes nothing.
-#include <stdlib.h>
 static inline int ps_env_int(const char* name, int dflt) { const char* e = getenv(name); return (e && *e) ? atoi(e) : dflt; }
 #ifdef PS_DIAG
 static inline int ps_diag_int(const char* name, int dflt) { return ps_env_int(name, dflt); }
@@ -391,7 +392,7 @@ struct GemmGroup {
   // once per tile pair (C2's grouped W2 / W1 / Wo gradients: FETCH_SIZE x2 = 143 MB per launch for 49.5 MB of operands, PMC)
   int flat_xcd;
   int split_xcd;      // the same placement on the 3-D grid (set by ps_launch_gemm: ta == 1, ksplit a multiple of 8)
-  // weight-gradient launches whose caller sized ksplit for 128x128 tiles: take gemm_x3d_kernel (tem.hip, run_wgrads)
+  // weight-gradient launches whose caller sized ksplit for 128x128 tiles: take gemm_x3d_kernel (wgrad.hip, run_wgrads)
   int prefer_x3d;
   // diagnostics (PS_GEMM_STAMP=1 + ps_debug_set_stamp_buffer, tools/gemm_stamps.py): the waves of one mid-grid workgroup of the
   // bf16x3 kernel record s_memtime at their phase boundaries, 32 slots per wave
@@ -400,14 +401,8 @@ struct GemmGroup {
 unsigned long long* ps_debug_stamp_ptr();
 
 int ps_launch_gemm(const GemmGroup& g, hipStream_t stream);
-// Fork of the side stream without a stream operation on the main stream (tem.hip, side_fork): the side stream waits for a
-// sequence value, and the NEXT kernel launched on the main stream stores it as its first workgroup starts — every earlier
-// main-stream kernel has completed by then (in-order stream), which is all a fork promises.  A launcher that can carry the
-// signal asks for it right before its launch; side_repend_signal hands it back when the launch did not happen (the join
-// flushes an unclaimed signal with a stream write).  The write-value operation this replaces cost the main stream ~5 us
-// between two dependent kernels, twice per backward.
-bool side_take_signal(hipStream_t st, uint32_t** flag, uint32_t* val);
-void side_repend_signal(hipStream_t st, uint32_t val);
+// Device side of a kernel-carried fork of the side stream (side_stream.h, side_take_signal): called first thing by every kernel
+// whose launcher may have taken a pending signal
 __device__ __forceinline__ void fork_signal(uint32_t* sig, uint32_t val) {
   if (sig && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
     __hip_atomic_store(sig, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -415,14 +410,17 @@ __device__ __forceinline__ void fork_signal(uint32_t* sig, uint32_t val) {
 // PS_DETERMINISTIC=1 / ps_set_deterministic(1): bitwise run-to-run reproducible TEM training steps — one stream,
 // weight gradients through per-split partials + an ordered sum, table scatters by sole-owner waves walking the tasks in order.
 bool ps_deterministic();
+bool stream_capturing(hipStream_t st);      // st is being captured into a graph (graph.h)
 // library-owned scratch: per device and slot (0: deterministic split reductions, 1: deterministic score backward, 2: the weight
-// planes of WPlaneScope), grow-only
+// planes of WPlaneScope), grow-only; null when it would have to grow on a capturing stream
+#define PS_MAX_DEVICES 16
 float* ps_det_scratch(int slot, size_t floats, hipStream_t st);
 // For its lifetime the listed fp32 weight matrices ([rows][cols], nn.Linear layout, row stride = cols) exist as bf16x3 plane
 // images in both orientations — split ONCE per entry-point call by one small launch on `st` — and ps_launch_gemm routes
 // products whose B operand is one of them (ta == 0, whole 32-deep slabs) to gemm_x3w_kernel, which no longer splits B at all
 // (and reads the transposed orientation for tb == 1: the dX products stop paying the row-contiguous loader).  Not nestable;
 // thread-local; nothing outlives the scope, so a weight the optimizer has moved is never multiplied through stale planes.
+bool gemm_x3_on();       // the bf16x3 products are enabled (ps_gemm_x3_config)
 bool gemm_x3w_on();
 struct WPlaneScope {
   WPlaneScope(hipStream_t st, const float* const* w, const int* rows, const int* cols, int n);

@@ -1,5 +1,5 @@
-// encoder.h — pieces of the TEM host orchestration (tem.hip) shared with the RTM path (rtm.hip):
-// the workspace layout and the transformer-encoder layer loops (forward / backward).
+// encoder.h — the transformer encoder shared by the item models (tem.hip) and the review transformer (rtm.hip), implemented in
+// encoder.hip: the workspace layout, the per-call plan and the layer loops (forward / backward).
 #pragma once
 #include "rowwise.h"
 
@@ -28,12 +28,11 @@ struct Ws {
   int64_t total;
 };
 
-
-#define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-
 int make_ws(const PsTemDesc& D, Ws& w);
 // the last layer's weights as the fused kernels' bf16x3 planes inside the workspace (on = 0 when the x3 form is not taken)
 WSplit make_wsplit(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w);
+// The encoder weights a WPlaneScope (common.h) should hold for this call; returns their number (at most PS_WPLANES_MAX)
+int wplane_list(const PsTemDesc& D, const PsTemTensors& P, const Ws& w, const float** ws_, int* rows, int* cols);
 
 // ------------------------------------------------------------- one plan per call
 // Which path every step of the encoder takes, decided once per call by enc_plan (host only, no launches) from the shapes, the
@@ -116,15 +115,3 @@ int ae_zoff(const PsTemDesc& D);
 int ae_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, float* ws, const Ws& w, hipStream_t st);
 int ae_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui, float* ws, const Ws& w,
                 hipStream_t st);
-
-GemmProblem gp(const float* A, int lda, int ta, const float* Bm, int ldb, int tb, float* C, int ldc, int M, int N, int K);
-int run1(const GemmProblem& p, hipStream_t st);
-GemmProblem gp_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int n_out, int k_in, int rows);
-int side_wgrads(GemmProblem* ps, int n, hipStream_t main_st);
-int main_wgrads(GemmProblem* ps, int n, hipStream_t st);   // the same weight-gradient launch on `st` itself
-int side_fork(hipStream_t main_st);
-int side_run(GemmProblem* ps, int n, hipStream_t main_st);
-int side_join(hipStream_t main_st);
-void side_abort();                                   // error paths: release a fork nobody will signal (tem.hip)
-void side_set_light(bool light);
-hipStream_t side_stream_or(hipStream_t main_st);   // the side stream, or main_st when it is disabled

@@ -30,6 +30,7 @@
 // 66 vs 44 us; weight gradients over 78k rows: 65 vs 49 us).  128-deep slabs for every launch cost the review
 // transformer 15 % (one workgroup per CU).
 #include "common.h"
+#include "side_stream.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -1329,7 +1330,7 @@ static void launch(int ta, int tb, dim3 grid, hipStream_t stream, const GemmGrou
 // PS_GEMM_X3: 0 = never, 1 (default) = wide products with enough tiles to fill the chip.  shape 2 = 128x128, 1 = 128x64,
 // 0 = 64x64 tiles; -1 = the fp32 kernel (small / latency-bound launches, where the deep-slab forms above matter more).
 // Measured at the d = 256 shard step (21,504 rows): 128x64 wins on every forward / dX product (128x128: 2 workgroups per
-// CU, 1.53 vs 1.41 ms per step), the weight gradients take 64x64 with the split counts tem.hip picks.
+// CU, 1.53 vs 1.41 ms per step), the weight gradients take 64x64 with the split counts wgrad.hip picks.
 static int g_x3_mode = -2, g_x3_force = -1;           // -2: not read yet
 extern "C" int ps_gemm_x3_config(int mode, int force_shape) {   // tests / experiments: mode 0|1, force_shape -1 (rule) | 0 | 1 | 2
   PS_REQUIRE((mode == 0 || mode == 1) && force_shape >= -1 && force_shape <= 4, "gemm x3 config %d %d", mode, force_shape);

@@ -44,6 +44,8 @@ inline uint64_t ps_fnv(uint64_t h, const void* p, size_t n) {
 }
 #define PS_FNV0 1469598103934665603ull
 
+// Several translation units include this header.  Its functions are `inline`, never `static inline`: the language then gives
+// the library ONE copy of each function-local static — one switch, one graph table, one capture stream.
 inline PsGraphEntry* ps_graph_lookup(uint64_t key) {
   static PsGraphEntry table[PS_GRAPH_SLOTS];
   static bool init = false;

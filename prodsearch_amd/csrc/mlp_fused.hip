@@ -27,10 +27,10 @@
 // Dropout masks of the three sites are the 16-bit column-shared Philox form (common.h): a lane's 8 consecutive features /
 // columns share one call.  Everything the backward needs (y1, ln1, a1, h1, y2, LN statistics) is still written once.
 #include "rowwise.h"
+#include "side_stream.h"
 #include "x3frag.h"
 #include <stdlib.h>
 #ifndef TRY
-#define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 #endif
 
 bool ps_fusion_enabled() {

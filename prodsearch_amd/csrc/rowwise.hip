@@ -5,6 +5,7 @@
 // fp32 work: rows are read with 16-byte lanes (coalesced 128 B..1 KiB per row),
 // reductions are wavefront shuffles, nothing here is reshaped into a GEMM.
 #include "rowwise.h"
+#include "side_stream.h"
 #include <stdlib.h>
 
 static inline int lpr_for(int d) {   // lanes per row for float4 lanes: pow2 >= d/4, <= 64

@@ -3,7 +3,7 @@
 //
 // Sequences are n = b*J + j (J = 1+K in training: j = 0 positive, j = 1+k negative k; J = C in
 // eval), S = R+1 positions: [query, R reviews].  Unlike TEM every sequence is distinct, so the
-// encoder (shared layer loops of tem.hip via encoder.h) runs on B*J sequences with no replica
+// encoder (the shared layer loops of encoder.hip) runs on B*J sequences with no replica
 // fan-out; only position 0 is consumed (TransformerEncoder.forward, transformer.py:90-98), so the
 // last layer is the one-query-row form.  RTM-specific kernels here:
 //   rtm_embed      review vectors (pv: row gather; pvc: masked mean of <= WL word rows per review with
@@ -15,6 +15,8 @@
 //   *_bwd          their backward: fp32-atomic scatter-adds into the dense table gradients
 #include "encoder.h"
 #include "rowwise.h"
+#include "side_stream.h"
+#include "wgrad.h"
 #include <string.h>
 
 #define SITE_REV_PV 0x200u
@@ -2352,6 +2354,6 @@ extern "C" int ps_rtm_backward(const PsRtmDesc* desc, const PsRtmTensors* params
   EncBwdOut out;
   const int rc = rtm_backward_impl(desc, params, batch, ws, grads, loss_scale, loss_scale_dev, stream, out);
   enc_record_backward(out);
-  if (rc != PS_OK) side_abort();    // never leave the side stream waiting behind a failed call (tem.hip)
+  if (rc != PS_OK) side_abort();    // never leave the side stream waiting behind a failed call (side_stream.h)
   return rc;
 }

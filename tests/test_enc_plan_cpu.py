@@ -1,4 +1,4 @@
-"""The encoder plan (csrc/tem.hip: enc_plan, through ps_tem_plan — host only, no device) against the hand-written table of
+"""The encoder plan (csrc/encoder.hip: enc_plan, through ps_tem_plan — host only, no device) against the hand-written table of
 tests/enc_paths.py, for every case of the table; the table's own coverage of the plan's cells; deterministic mode; and every
 supported switch's effect on the plan, one child process per switch (the switches are read once per process).  The GPU tests
 assert the same rows against what a step really launched (tests/test_gpu_enc_paths.py)."""

@@ -168,7 +168,7 @@ def test_c5_shard_dropout_step_matches_the_replicated_oracle():
     structure (item_transformer.py:471-494: the encoder on B and on B*K expanded copies) on the compacted table, with the
     product's Philox masks injected: loss / ps / item loss and the [1024, 21] logits <= 1e-4, the gradient of every tensor
     <= 5e-4 of its max, touched rows of both tables bit-exact.  Only at this size does the step select the 128x128
-    direct-to-LDS weight gradients (gemm_x3d_kernel, tem.hip `t128 * ks3 >= 384`), fanin_sum_kernel and the row-list K/V dX
+    direct-to-LDS weight gradients (gemm_x3d_kernel, wgrad.hip `t128 * ks3 >= 384`), fanin_sum_kernel and the row-list K/V dX
     product; the oracle side is ~1 minute and ~20 GB of host memory."""
     from oracle import tem as otem, philox
     a, wd, m, optim, batch, ni, nw = _setup(0.1)

@@ -1,7 +1,7 @@
 """A backward that fails between a side-stream fork and its join must surface as an exception, not as a hang.
 
 The default step parks the side stream on ``hipStreamWaitValue32`` and lets the NEXT main-stream kernel store the value
-(csrc/tem.hip, side_fork / side_take_signal).  If the call fails before that kernel is launched nobody stores it; the
+(csrc/side_stream.hip, side_fork / side_take_signal).  If the call fails before that kernel is launched nobody stores it; the
 entry points therefore release the fork on every non-OK exit (``side_abort``).  ``ps_debug_fail_fork(n)`` injects exactly
 that failure.  The scenario runs in a child process with a timeout so that a regression cannot stall the whole suite
 (trainer.py:74-79 call order)."""

@@ -1,4 +1,4 @@
-"""The side stream's value crossings (csrc/tem.hip: hipStreamWaitValue32 on the side stream, the value stored by the next
+"""The side stream's value crossings (csrc/side_stream.hip: hipStreamWaitValue32 on the side stream, the value stored by the next
 main-stream kernel) under conditions that could starve them, each in a fresh child process with a timeout — a stall must
 show up as a failed test, never as a hung suite (trainer.py:74-79 call order throughout):
   * the start-up self-test: forced to fail it must fall back to event pairs (ps_side_values_in_use() == 0) and train the same;
