@@ -582,6 +582,17 @@ float ps_dropout_mult_host(const PsTemDesc* desc, uint32_t site, uint32_t row, u
 int ps_ktimer_arm(const char* tag, int32_t max_samples);
 int ps_ktimer_read(double* avg_us, double* min_us, int32_t* count);
 
+/* Tuning knob (no reference counterpart): weight-gradient groups with row-list members at d = 128 (K / V / Q and the deferred
+ * K / V / Q / f_W group) give every member its own split count in one flat launch (default 1, env PS_KVQ_SPLIT; 0 = one common
+ * count on the 3-D grid).  Deterministic mode never takes the form.  Returns the previous value. */
+int ps_set_kvq_split(int on);
+/* Unit-test hook of the grouped weight-gradient launch: member i (n <= 4) adds dY[i][rows[i], n_out]^T . X[i][rows[i], k_in] onto
+ * dW[i][n_out, k_in]; listed[i] != 0: over the *rcount rows ridx[0 .. *rcount) only (device memory; rows[i] bounds the list, ridx has
+ * room for rows[i] entries).  ks_listed / ks_plain > 0 replace the per-member split counts where that form is taken. */
+int ps_wgrad_group_test(int n, const float* const* dY, const float* const* X, float* const* dW, const int32_t* rows,
+                        const int32_t* listed, const int32_t* ridx, const int32_t* rcount, int n_out, int k_in,
+                        int ks_listed, int ks_plain, ps_stream_t stream);
+
 /* Unit-test hook of the fp32 MFMA GEMM: C[M,N] = alpha * op(A) op(B) (+bias) (+C if accumulate).
  * ta: A stored [K,M];  tb==0: B stored [N,K] (nn.Linear), tb==1: B stored [K,N]. */
 int ps_gemm_f32(const float* A, int lda, int ta, const float* Bm, int ldb, int tb,

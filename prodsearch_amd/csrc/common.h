@@ -379,24 +379,28 @@ struct GemmProblem {
 };
 
 struct GemmGroup {
-  GemmProblem p[4];      // (the flat form below holds at most three)
+  GemmProblem p[4];
   int n;
   // a fork of the side stream signalled by THIS launch: its first workgroup stores sigval to *sig as it starts (side_take_signal)
   uint32_t* sig; uint32_t sigval;
   // flat form (weight gradients of different shapes in one launch): grid.x walks  sum_i tiles_i * ksplit_i  workgroups,
-  // problem i owns [flat0[i], flat0[i+1]): split-major, then row tile, then column tile; each problem keeps its own ksplit
+  // problem i owns [flat0[i], flat0[i+1]): split-major, then row tile, then column tile; each problem keeps its own ksplit.
+  // Members may carry a row list (the fp32 kernel's IDX form): their split count is the host's, their slab count the device's.
   int flat;
-  int flat0[4], flat_tm[3], flat_tiles[3];
-  // flat_xcd: workgroup L runs on XCD L % 8 (round-robin dispatch); with every flat0[] and ksplit a multiple of 8 the decode puts ALL
-  // tiles of a reduction split on one XCD (split % 8 == L % 8), so the split's operand rows cross the fabric once per XCD instead of
-  // once per tile pair (C2's grouped W2 / W1 / Wo gradients: FETCH_SIZE x2 = 143 MB per launch for 49.5 MB of operands, PMC)
+  int flat0[5], flat_tm[4], flat_tiles[4];
+  // flat_xcd (bit i: problem i): workgroup L runs on XCD L % 8 (round-robin dispatch); with flat0[i] and the problem's ksplit a multiple
+  // of 8 the decode puts ALL tiles of a reduction split on one XCD (split % 8 == L % 8), so the split's operand rows cross the fabric
+  // once per XCD instead of once per tile pair (C2's grouped W2 / W1 / Wo gradients: FETCH_SIZE x2 = 143 MB per launch for 49.5 MB of
+  // operands, PMC).  Plain groups place all members or none; a group with listed members places each member that qualifies.
   int flat_xcd;
   int split_xcd;      // the same placement on the 3-D grid (set by ps_launch_gemm: ta == 1, ksplit a multiple of 8)
   // weight-gradient launches whose caller sized ksplit for 128x128 tiles: take gemm_x3d_kernel (wgrad.hip, run_wgrads)
   int prefer_x3d;
   // diagnostics (PS_GEMM_STAMP=1 + ps_debug_set_stamp_buffer, tools/gemm_stamps.py): the waves of one mid-grid workgroup of the
-  // bf16x3 kernel record s_memtime at their phase boundaries, 32 slots per wave
+  // bf16x3 kernel record s_memtime at their phase boundaries, 32 slots per wave.  stamp_kvq (PS_GEMM_STAMP=5, the fp32 kernel):
+  // split 1, tile (0, 0) of members 0 and 2 of a listed weight-gradient group stamp instead, at stamp + 256 and stamp + 384
   unsigned long long* stamp;
+  int stamp_kvq;
 };
 unsigned long long* ps_debug_stamp_ptr();
 

@@ -116,6 +116,25 @@ __device__ __forceinline__ void epi_plain(const GemmProblem& P, const f32x16& ac
   const float alpha = P.alpha;
   float* const C = P.C + (size_t)split * P.split_stride;
   const int ldc = P.ldc, accumulate = P.accumulate;
+  if (accumulate == 2) {
+    // split reduction (kernel-uniform): sixteen atomics in a straight line.  In the general loop below every row sits under its own
+    // test beside the load + store of `accumulate == 1`, and the compiler opened each row's block with s_waitcnt vmcnt(0): a wave
+    // waited for the previous row's atomic to be ACKNOWLEDGED before it issued the next — sixteen dependent round trips, 15,000 of
+    // the 42,000 cycles a K / V weight-gradient workgroup lived at C2 (profiles/kvq_wgrad_notes.md).  No test here:
+    // a row or column past the edge adds 0.f to the last real one.
+    const int ccol = min(col, N - 1);
+    size_t off[16];
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, rr = min(row, M - 1);
+      off[r] = (size_t)((listed && TA == 0) ? (rows_s ? rows_s[rr - m0] : P.ridx[rr]) : rr) * ldc + ccol;
+      v[r] = (col_ok && row < M) ? (acc[r] + bias) * alpha : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) atomicAdd(&C[off[r]], v[r]);
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -266,14 +285,16 @@ __device__ __forceinline__ void epi_full(const GemmProblem& P, const float (*Ct)
 
 #define KIDX_MAX PS_GEMM_KIDX_MAX
 // diagnostics (PS_GEMM_STAMP=2 / 3, tools/gemm_f32_stamps.py): s_memtime of the four waves of workgroup (0, 8, 0) at the phase
-// boundaries of the fp32 kernel — the step's own dX product over the row list (2) or its K/V projection (3)
+// boundaries of the fp32 kernel — the step's own dX product over the row list (2) or its K/V projection (3); 5 (GemmGroup::stamp_kvq):
+// one listed and one plain workgroup of the deferred K / V / Q / f_W weight gradients, chosen once the decode knows who they are
 #if PS_DIAG_ON      // in-kernel phase stamps: diagnostic build only
+#define F32_NOW(t_) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory")
 #define F32_STAMP(slot)                                                                                              \
   do {                                                                                                               \
-    if (g.stamp && blockIdx.x == 0 && blockIdx.y == 8 && blockIdx.z == 0 && (threadIdx.x & 63) == 0) {               \
+    if (stamp_off >= 0 && (threadIdx.x & 63) == 0) {                                                                 \
       unsigned long long t_;                                                                                         \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                                     \
-      if ((slot) < 32) g.stamp[32 * (threadIdx.x >> 6) + (slot)] = t_;                                               \
+      F32_NOW(t_);                                                                                                   \
+      if ((slot) < 32) g.stamp[stamp_off + 32 * (threadIdx.x >> 6) + (slot)] = t_;                                   \
     }                                                                                                                \
   } while (0)
 #else
@@ -282,6 +303,11 @@ __device__ __forceinline__ void epi_full(const GemmProblem& P, const float (*Ct)
 template <int TA, int TB, int FULL, int BK, int PF, int IDX = 0>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmGroup g) {
   fork_signal(g.sig, g.sigval);
+#if PS_DIAG_ON
+  int stamp_off = (g.stamp && !g.stamp_kvq && blockIdx.x == 0 && blockIdx.y == 8 && blockIdx.z == 0) ? 0 : -1;
+  unsigned long long stamp_t0 = 0;
+  if (g.stamp && g.stamp_kvq) F32_NOW(stamp_t0);
+#endif
   F32_STAMP(0);
   constexpr int NLD = BK / 16;
   __shared__ float As[2][BK][LDT];
@@ -292,9 +318,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmGroup g) {
   int prob, split, ftile = 0;
   if (g.flat) {
     const int L = blockIdx.x;
-    prob = L >= g.flat0[2] ? 2 : (L >= g.flat0[1] ? 1 : 0);
+    prob = L >= g.flat0[3] ? 3 : (L >= g.flat0[2] ? 2 : (L >= g.flat0[1] ? 1 : 0));
     const int t = L - g.flat0[prob];
-    if (g.flat_xcd) {
+    if ((g.flat_xcd >> prob) & 1) {
       const int s8 = t >> 3, grp = s8 / g.flat_tiles[prob];
       split = (t & 7) + 8 * grp;
       ftile = s8 - grp * g.flat_tiles[prob];
@@ -333,6 +359,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmGroup g) {
     tn = r / rows_here;
   }
   const int m0 = tm * BM, n0 = tn * BN;
+#if PS_DIAG_ON
+  if (g.stamp && g.stamp_kvq && split == 1 && tm == 0 && tn == 0 && (prob == 0 || prob == 2)) {
+    stamp_off = 256 + 64 * prob;
+    if ((threadIdx.x & 63) == 0) g.stamp[stamp_off + 32 * (threadIdx.x >> 6)] = stamp_t0;
+  }
+#endif
   // row list, ta == 0: the tile's 64 list entries are fetched NOW, beside the list length (the list has room for P.M
   // entries, common.h; what lies past the length is never used), and kept in LDS for the operand loads and the epilogue
   // — after the length they were a second dependent round trip here and a third in front of every epilogue row group
@@ -604,9 +636,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmGroup g) {
   int prob, split, ftile = 0;
   if (g.flat) {
     const int L = blockIdx.x;
-    prob = L >= g.flat0[2] ? 2 : (L >= g.flat0[1] ? 1 : 0);
+    prob = L >= g.flat0[3] ? 3 : (L >= g.flat0[2] ? 2 : (L >= g.flat0[1] ? 1 : 0));
     const int t = L - g.flat0[prob];
-    if (g.flat_xcd) {
+    if ((g.flat_xcd >> prob) & 1) {
       const int s8 = t >> 3, grp = s8 / g.flat_tiles[prob];
       split = (t & 7) + 8 * grp;
       ftile = s8 - grp * g.flat_tiles[prob];
@@ -849,9 +881,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3d_kernel(const GemmGroup g) {
   int prob, split, ftile = 0;
   if (g.flat) {
     const int L = blockIdx.x;
-    prob = L >= g.flat0[2] ? 2 : (L >= g.flat0[1] ? 1 : 0);
+    prob = L >= g.flat0[3] ? 3 : (L >= g.flat0[2] ? 2 : (L >= g.flat0[1] ? 1 : 0));
     const int t = L - g.flat0[prob];
-    if (g.flat_xcd) {
+    if ((g.flat_xcd >> prob) & 1) {
       const int s8 = t >> 3, grp = s8 / g.flat_tiles[prob];
       split = (t & 7) + 8 * grp;
       ftile = s8 - grp * g.flat_tiles[prob];
@@ -1465,47 +1497,60 @@ int ps_launch_gemm(const GemmGroup& g0, hipStream_t stream) {
   static const int stamps = ps_diag_int("PS_GEMM_STAMP", 0);
   const bool stamp_this = stamps == 1 || (stamps == 2 && g0.p[0].ridx && g0.p[0].res.mode == RES_FANIN) ||
                           (stamps == 3 && g0.p[0].ridx && !g0.p[0].ta && g0.p[0].res.mode == RES_NONE) ||
-                          (stamps == 4 && g0.n == 3 && g0.p[0].ta && !g0.p[0].ridx);      // 4: the grouped FF / Wo weight gradients
+                          (stamps == 4 && g0.n == 3 && g0.p[0].ta && !g0.p[0].ridx) ||    // 4: the grouped FF / Wo weight gradients
+                          (stamps == 5 && g0.n == 4 && g0.p[0].ta && g0.p[0].ridx);       // 5: the deferred K / V / Q / f_W weight gradients
   g.stamp = stamp_this ? ps_debug_stamp_ptr() : nullptr;
+  g.stamp_kvq = stamps == 5;
   const bool took = side_take_signal(stream, &g.sig, &g.sigval);      // a pending fork of the side stream rides on this launch
   const int rc = launch_gemm_impl(g, stream);
   if (took && rc != PS_OK) side_repend_signal(stream, g.sigval);
   return rc;
 }
 static int launch_gemm_impl(const GemmGroup& g, hipStream_t stream) {
-  PS_REQUIRE(g.n >= 1 && g.n <= (g.flat ? 3 : 4), "gemm: group size %d", g.n);
+  PS_REQUIRE(g.n >= 1 && g.n <= 4, "gemm: group size %d", g.n);
   if (g.flat) {
+    bool listed = false;
     for (int i = 0; i < g.n; ++i) {
       int rc = validate(g.p[i]);
       if (rc) return rc;
-      PS_REQUIRE(g.p[i].ta == 1 && g.p[i].tb == 1 && !needs_full(g.p[i]) && !g.p[i].ridx && g.p[i].ksplit >= 1 &&
-                 (g.p[i].accumulate == 2 || (g.p[i].accumulate == 0 && g.p[i].split_stride > 0)),
-                 "gemm: the flat group form takes plain weight-gradient problems");
+      const GemmProblem& p = g.p[i];
+      PS_REQUIRE(p.ta == 1 && p.tb == 1 && !needs_full(p) && p.ksplit >= 1 &&
+                 (p.accumulate == 2 || (p.accumulate == 0 && p.split_stride > 0)),
+                 "gemm: the flat group form takes weight-gradient problems");
+      if (!p.ridx) continue;
+      listed = true;
+      const int per = ps_cdiv(ps_cdiv(p.K, 32), p.ksplit);
+      PS_REQUIRE(p.rcount && p.kseg >= p.K && !p.bias && per * 32 <= KIDX_MAX,
+                 "gemm: flat row-list weight gradient: one segment, no bias, %d rows per split <= %d", per * 32, KIDX_MAX);
     }
     // the bf16x3 forms (the same flat tables): C2's W2 / W1 / Wo weight gradients 0.2905 -> 0.2845 ms per step with 64x64 tiles
-    // (round 2); 128x128 tiles of the direct-to-LDS form where x3_flat_shape() says so
+    // (round 2); 128x128 tiles of the direct-to-LDS form where x3_flat_shape() says so.  Groups with listed members: the fp32 kernel
     static const int flat_x3 = ps_diag_int("PS_GEMM_X3_FLAT", 1);
-    const bool x3 = flat_x3 && x3_on();
+    const bool x3 = flat_x3 && x3_on() && !listed;
     const bool x3d = x3 && (x3_flat_d(g) || g.prefer_x3d) && x3d_takes(g);
     static const int flat_shape = ps_diag_int("PS_X3_FLAT_SHAPE", 0);      // 1: 128x64, 2: 128x128 tiles of gemm_x3_kernel
     const int fs = (x3 && !x3d) ? flat_shape : 0;
     const int TM = x3d ? X3D_T : (fs >= 1 ? 128 : BM), TN = x3d ? X3D_T : (fs == 2 ? 128 : BM);
     GemmGroup f = g;
     int total = 0;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 4; ++i) {
       f.flat0[i] = total;
       if (i >= g.n) { f.flat_tm[i] = 1; f.flat_tiles[i] = 1; continue; }
       f.flat_tm[i] = ps_cdiv(g.p[i].M, TM);
       f.flat_tiles[i] = f.flat_tm[i] * ps_cdiv(g.p[i].N, TN);
       total += f.flat_tiles[i] * g.p[i].ksplit;
     }
-    f.flat0[3] = total;
-    for (int i = g.n; i < 3; ++i) f.flat0[i] = total + 1;      // never selected
+    f.flat0[4] = total;
+    for (int i = g.n; i < 4; ++i) f.flat0[i] = total + 1;      // never selected
     static const int flat_xcd = ps_diag_int("PS_FLAT_XCD", 1);
-    f.flat_xcd = flat_xcd;
-    for (int i = 0; i < g.n; ++i)
-      if (g.p[i].ksplit % 8 != 0 || f.flat0[i] % 8 != 0) f.flat_xcd = 0;
-    if (x3d) PS_KLAUNCH((gemm_x3d_kernel<1, 1, 0, 0>), dim3(total, 1, 1), dim3(256), 0, stream, f);
+    f.flat_xcd = 0;
+    for (int i = 0; i < g.n && flat_xcd; ++i)
+      if (g.p[i].ksplit % 8 == 0 && f.flat0[i] % 8 == 0) f.flat_xcd |= 1 << i;
+    if (!listed && f.flat_xcd != (1 << g.n) - 1) f.flat_xcd = 0;
+    // listed groups: their workgroups run 2-3 slabs at the list lengths the step produces, so ALL of a short reduction's operand
+    // slabs are requested before the first is consumed (PF = 3; longer lists refill the slots as any PF does)
+    if (listed) PS_KLAUNCH((gemm_f32_kernel<1, 1, 0, 32, 3, 1>), dim3(total, 1, 1), dim3(256), 0, stream, f);
+    else if (x3d) PS_KLAUNCH((gemm_x3d_kernel<1, 1, 0, 0>), dim3(total, 1, 1), dim3(256), 0, stream, f);
     else if (x3 && fs == 2) PS_KLAUNCH((gemm_x3_kernel<1, 1, 0, 2, 2, 0, 1>), dim3(total, 1, 1), dim3(256), 0, stream, f);
     else if (x3 && fs == 1) PS_KLAUNCH((gemm_x3_kernel<1, 1, 0, 2, 1, 0, 1>), dim3(total, 1, 1), dim3(256), 0, stream, f);
     else if (x3) PS_KLAUNCH((gemm_x3_kernel<1, 1, 0, 1, 1, 0, 1>), dim3(total, 1, 1), dim3(256), 0, stream, f);
@@ -1545,8 +1590,7 @@ static int launch_gemm_impl(const GemmGroup& g, hipStream_t stream) {
   {
     static const int flat_all = ps_diag_int("PS_WGRAD_FLAT_ALL", 1);
     const int ks = g.p[0].ksplit;
-    // (the flat decode holds at most 3 problems: the deferred K / V / Q + f_W group of the item transformer has 4)
-    bool plain = flat_all && !listed && !full && g.n <= 3 && g.p[0].ta == 1 && g.p[0].tb == 1 && ks >= 8 && ks % 8 == 0 && x3_on();
+    bool plain = flat_all && !listed && !full && g.p[0].ta == 1 && g.p[0].tb == 1 && ks >= 8 && ks % 8 == 0 && x3_on();
     for (int i = 0; i < g.n && plain; ++i)
       plain = g.p[i].accumulate == 2 || (g.p[i].accumulate == 0 && g.p[i].split_stride > 0);
     if (plain) {

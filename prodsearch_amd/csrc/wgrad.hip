@@ -93,6 +93,39 @@ static int run_wgrads_det(GemmGroup& g, hipStream_t st) {
 // the last arriver of a tile adds the partials up in split order — deterministic and free of fp32 atomics, but 122 us against
 // 44 for the grouped launch at C2 and 0.395 against 0.292 ms per step: the device-scope release each of the 600 workgroups
 // needs before its ticket writes back its XCD's L2, MI300-class L2s not being coherent with one another)
+// Groups with row-list members at the item transformer's d = 128 shapes (the deferred K / V / Q / f_W group of the C2 step, the
+// K / V / Q group of the unfused paths): every member its own split count, one flat launch (profiles/kvq_wgrad_notes.md).
+//   listed member: the host knows the position count only; the list the step really produces holds about a third of it (C2: ~2,900
+//     of 8,064).  One split per 288 positions is three 32-row slabs at that length, all three requested before the first is used
+//     (ps_launch_gemm, PF = 3); a full list is nine slabs per split, an empty one none — correct at any length.
+//   plain member (Q, f_W: one row per sequence): a split per 64 rows (two slabs; with four the Q workgroups were the launch's longest),
+//     not one per 32-row slab; at most the 16 the common count gave.
+// The common count of the 3-D grid came from the largest K: 16 splits of six serial slabs for K / V on 128 of 256 CUs, and twelve
+// one-slab workgroups with a 16 KB atomic tile each for Q and for f_W.  PS_KVQ_SPLIT=0 / ps_set_kvq_split(0): that form.
+// Measured at C2 only, so the rule keeps to outputs of at most 128 x 128 and at most 16,384 positions: the review transformer's 78k
+// positions and the d = 256 shard keep the common count.  Never in deterministic mode.
+static int& kvq_split_slot() { static int v = ps_env_int("PS_KVQ_SPLIT", 1); return v; }
+extern "C" int ps_set_kvq_split(int on) { const int was = kvq_split_slot(); kvq_split_slot() = on; return was; }
+static int g_kvq_force[2] = {0, 0};      // ps_wgrad_group_test / the sweep: split counts of the listed and the plain members (0: the rule)
+static bool kvq_split_takes(const GemmProblem* ps, int n) {
+  if (!kvq_split_slot() || ps_deterministic() || n < 2) return false;
+  bool listed = false;
+  for (int i = 0; i < n; ++i) {
+    if (ps[i].M > 128 || ps[i].N > 128 || ps[i].K > 16384 || !(ps[i].ta == 1 && ps[i].tb == 1)) return false;
+    listed = listed || ps[i].ridx;
+  }
+  return listed;
+}
+static int kvq_ksplit(const GemmProblem& p) {
+  static const int diag_listed = ps_diag_int("PS_KVQ_KS", 0), diag_plain = ps_diag_int("PS_KVQ_KS_PLAIN", 0);   // the sweep
+  const int forced = p.ridx ? (g_kvq_force[0] ? g_kvq_force[0] : diag_listed) : (g_kvq_force[1] ? g_kvq_force[1] : diag_plain);
+  int ks = forced > 0 ? forced : (p.ridx ? ps_cdiv(p.K, 288) : (p.K / 64 < 16 ? p.K / 64 : 16));
+  const int need = p.ridx ? ps_cdiv(ps_cdiv(p.K, 32) * 32, PS_GEMM_KIDX_MAX - 32) : 1;     // one split's rows map through LDS
+  if (ks < need) ks = need;
+  if (forced <= 0 && ks > 8 && ks % 8 != 0) ks = (ks + 7) / 8 * 8;      // GemmGroup::flat_xcd
+  return ks < 1 ? 1 : ks;
+}
+
 int run_wgrads(GemmProblem* ps, int n, hipStream_t st) {
   GemmGroup g;
   memset(&g, 0, sizeof(g));
@@ -101,6 +134,11 @@ int run_wgrads(GemmProblem* ps, int n, hipStream_t st) {
   for (int i = 0; i < n; ++i) {
     same = same && ps[i].M == ps[0].M && ps[i].N == ps[0].N && ps[i].K == ps[0].K;
     plain = plain && !ps[i].ridx;
+  }
+  if (kvq_split_takes(ps, n)) {
+    for (int i = 0; i < n; ++i) { g.p[i] = ps[i]; g.p[i].ksplit = kvq_ksplit(ps[i]); }
+    g.flat = 1;
+    return ps_launch_gemm(g, st);
   }
   if (n > 1 && n <= 3 && !same && plain) {
     // different shapes in one launch: the flat form (GemmGroup::flat) — every problem keeps the split count it would
@@ -150,4 +188,22 @@ int side_run(GemmProblem* ps, int n, hipStream_t main_st) {
 int side_wgrads(GemmProblem* ps, int n, hipStream_t main_st) {
   TRY(side_fork(main_st));
   return side_run(ps, n, main_st);
+}
+
+// Test hook (tests/test_gpu_wgrad_listed.py): one weight-gradient group from raw pointers through run_wgrads.  Member i:
+// dW[i][n_out, k_in] += dY[i][rows[i], n_out]^T . X[i][rows[i], k_in]; listed[i] != 0: over the *rcount rows ridx[0..] only (rows[i]
+// bounds the list).  ks_listed / ks_plain > 0 replace the rule's split counts where the per-member form is taken.
+extern "C" int ps_wgrad_group_test(int n, const float* const* dY, const float* const* X, float* const* dW, const int32_t* rows,
+                                   const int32_t* listed, const int32_t* ridx, const int32_t* rcount, int n_out, int k_in,
+                                   int ks_listed, int ks_plain, ps_stream_t stream) {
+  PS_REQUIRE(n >= 1 && n <= 4 && ks_listed >= 0 && ks_plain >= 0, "wgrad group test: %d members", n);
+  GemmProblem ps[4];
+  for (int i = 0; i < n; ++i) {
+    ps[i] = gp_wgrad(dY[i], n_out, X[i], k_in, dW[i], n_out, k_in, rows[i]);
+    if (listed[i]) { PS_REQUIRE(ridx && rcount, "wgrad group test: listed member without a list"); ps[i].ridx = ridx; ps[i].rcount = rcount; }
+  }
+  g_kvq_force[0] = ks_listed; g_kvq_force[1] = ks_plain;
+  const int rc = run_wgrads(ps, n, (hipStream_t)stream);
+  g_kvq_force[0] = g_kvq_force[1] = 0;
+  return rc;
 }
