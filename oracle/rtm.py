@@ -62,7 +62,7 @@ def rtm_forward(P, args, batch, neg_word_idxs, vocab_size, review_count, trainin
     K = neg_r.shape[1]
     d = args.embedding_size
     pe = positional_encoding(5000, d)
-    query_emb, _, _ = query_encode(P, args, qw, word_pad, drop)                       # :257-258
+    query_emb, _, _ = query_encode(P, args, qw, word_pad, drop, keep)                 # :257-258
     pv_loss = None
     if enc_name == 'pv':
         table = P['review_encoder.review_embeddings.weight']
@@ -137,7 +137,8 @@ def rtm_forward(P, args, batch, neg_word_idxs, vocab_size, review_count, trainin
     k0 = {} if keep is not None else None
     te = 'transformer_encoder.'
     top_p = encoder_encode(P, args, pos_seq, pos_mask, pe, drop, 0, k0)                           # :336
-    top_n = encoder_encode(P, args, neg_seq.reshape(B * K, R + 1, d), neg_mask.reshape(B * K, R + 1), pe, drop, 1)
+    k1 = {} if keep is not None else None
+    top_n = encoder_encode(P, args, neg_seq.reshape(B * K, R + 1, d), neg_mask.reshape(B * K, R + 1), pe, drop, 1, k1)
     pos_scores = F.linear(top_p[:, 0, :], P[te + 'wo.weight'], P[te + 'wo.bias']).squeeze(-1)   # transformer.py:95-96
     neg_scores = F.linear(top_n[:, 0, :], P[te + 'wo.weight'], P[te + 'wo.bias']).squeeze(-1).view(B, K)
     pos_weight = K if args.pos_weight else 1
@@ -148,6 +149,7 @@ def rtm_forward(P, args, batch, neg_word_idxs, vocab_size, review_count, trainin
     loss = ps_loss + pv_loss if pv_loss is not None else ps_loss                                  # :357
     if keep is not None:
         keep.update(k0)
+        keep['neg'] = k1               # the negatives' encode, as the positives' at the top level (bookkeeping only)
         keep.update(query_emb=query_emb, pos_rev=pos_rev, neg_rev=neg_rev, scores=scores,
                     enc_pos=top_p[:, 0, :], enc_neg=top_n[:, 0, :].view(B, K, d),
                     pos_seq=pos_seq, neg_seq=neg_seq, pos_mask=pos_mask, neg_mask=neg_mask, weight=weight)

@@ -59,14 +59,18 @@ class TorchDropout(object):
         return F.dropout(x, self.p, True)
 
 
-def query_encode(P, args, query_word_idxs, word_pad_idx, drop):
+def query_encode(P, args, query_word_idxs, word_pad_idx, drop, keep=None):
     """``word_embeddings`` gather + ``FSEncoder.forward`` (text_encoder.py:32-40) or
-    ``AVGEncoder.forward`` (:76-83); call site item_transformer.py:449-450."""
+    ``AVGEncoder.forward`` (:76-83); call site item_transformer.py:449-450.
+    ``keep['fs_pre']``: the FS projection's pre-activation (bookkeeping only)."""
     emb = P['word_embeddings.weight'][query_word_idxs]
     mean = vector_mean(emb, query_word_idxs.ne(word_pad_idx))
     mean_d = drop(mean, 'fs', 0)
     if args.query_encoder_name == 'fs':
-        q = torch.tanh(F.linear(mean_d, P['query_encoder.f_W.weight'], P['query_encoder.f_W.bias']))
+        u = F.linear(mean_d, P['query_encoder.f_W.weight'], P['query_encoder.f_W.bias'])
+        if keep is not None:
+            keep['fs_pre'] = u
+        q = torch.tanh(u)
     else:
         q = mean_d
     return q, mean, mean_d
@@ -191,7 +195,7 @@ def tem_forward(P, args, batch, neg_item_idxs, neg_word_idxs, vocab_size, produc
     K = neg_item_idxs.shape[1]
     d = args.embedding_size
     pe = positional_encoding(5000, d)
-    query_emb, qmean, _ = query_encode(P, args, qw, word_pad, drop)
+    query_emb, qmean, _ = query_encode(P, args, qw, word_pad, drop, keep)
     u_mask = ui.ne(prod_pad)
     seq_mask = torch.cat([torch.ones(B, 1, dtype=torch.bool), u_mask], dim=1)      # :451-454
     hist_tab = P['hist_product_emb.weight'] if args.sep_prod_emb else P['product_emb.weight']
@@ -208,8 +212,11 @@ def tem_forward(P, args, batch, neg_item_idxs, neg_word_idxs, vocab_size, produc
         neg_seq = torch.cat([query_emb.unsqueeze(1).expand(-1, K, -1).unsqueeze(2),
                              u_emb.unsqueeze(1).expand(-1, K, -1, -1)], dim=2)      # :473-476
         neg_mask = seq_mask.unsqueeze(1).expand(-1, K, -1)                          # :458-460
+        k1 = {} if keep is not None else None
         top_n = encoder_encode(P, args, neg_seq.reshape(B * K, L + 1, d),
-                               neg_mask.reshape(B * K, L + 1), pe, drop, 1)         # :486-491
+                               neg_mask.reshape(B * K, L + 1), pe, drop, 1, k1)     # :486-491
+        if keep is not None:
+            keep['neg'] = k1           # the negatives' encode, as the positives' at the top level (bookkeeping only)
         neg_out = top_n[:, out_pos, :].view(B, K, d)
     else:
         neg_out = pos_out.unsqueeze(1).expand(-1, K, -1)
@@ -264,7 +271,7 @@ def qem_forward(P, args, batch, neg_item_idxs, neg_word_idxs, vocab_size, produc
     word_pad = vocab_size - 1
     tgt = batch.target_prod_idxs
     K = neg_item_idxs.shape[1]
-    query_emb, qmean, _ = query_encode(P, args, batch.query_word_idxs, word_pad, drop)
+    query_emb, qmean, _ = query_encode(P, args, batch.query_word_idxs, word_pad, drop, keep)
     target_emb = P['product_emb.weight'][tgt]
     neg_emb = P['product_emb.weight'][neg_item_idxs]
     pos_scores = (query_emb * target_emb).sum(-1)
