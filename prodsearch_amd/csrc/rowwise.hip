@@ -1940,7 +1940,7 @@ __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void embed_scatter_det_kern
 
 // table[keys[t]] += [scale[t] *] src[(rowidx ? rowidx[t] : t) * ld .. + d)  for t < ntask (keys[t] < 0: no task), deterministically: every table row has one
 // owner half-wave, which walks the tasks in task order (det_owner_walk) — the review transformer's user / item embedding
-// gradients in deterministic mode (rtm.hip)
+// gradients in deterministic mode (rtm_embed_bwd.hip; the PV loss's word rows: rtm_score.hip)
 template <int EPL>
 __global__ __launch_bounds__(32 * SBD_OWNERS_PER_WG) void rows_scatter_det_kernel(const int32_t* keys, int ntask, const float* src,
                                                                                  int64_t ld, int d, float* table, const float* scale,

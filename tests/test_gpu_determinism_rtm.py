@@ -1,4 +1,4 @@
-"""Deterministic mode of the review transformer (``ps_set_deterministic`` / PS_DETERMINISTIC=1; csrc/rtm.hip): the training step
+"""Deterministic mode of the review transformer (``ps_set_deterministic`` / PS_DETERMINISTIC=1; csrc/rtm_index.hip, rtm_embed_bwd.hip, rtm_score.hip): the training step
 of ``ProductRanker`` with a word-mean review encoder (pvc = BASELINE configs[3], fs, avg) is bitwise reproducible — the word
 index hands out its ranks in task order (one wave per partition, no atomics), a word's occurrences are summed in list order by
 one wave (sixteen fixed slices for the Zipf heads), d wo / d query_emb / the fs bias as fixed-order sums, weight gradients as

@@ -1,5 +1,5 @@
 """Review transformer on pretrained / fixed paragraph vectors on an MI355X, through the C ABI (``PsRtmDesc.frozen_mask`` /
-``no_pv_drop``, NULL table gradients, the frozen forms of csrc/rtm.hip):
+``no_pv_drop``, NULL table gradients, the frozen forms of csrc/rtm_embed_bwd.hip and rtm_score.hip):
 
 * every ``rtmpre_*`` fixture of the reference (tests/golden/make_golden_rtm_pretrained.py): loss terms, ``test()`` scores, every
   gradient, which are None, the frozen tables bitwise after three clipped Adam steps, the stepped parameters;

@@ -8,7 +8,7 @@ softmax row is near uniform and tanh / GELU / BCE sit in their linear range.  He
     LayerNorm stages on large rows.  tests/test_saturated_cpu.py asserts on the CPU that each case is in its regime and that
     fp32 arithmetic's own error there stays below 1e-4 — so the suite's bounds hold against float64: loss and logits 1e-4,
     every gradient 5e-4 of its max, the query words' rows of word_embeddings on their own, eval scores 1e-4;
-  * the 64-bit fixed-point loss hand-off of the folded scoring (csrc/mlp_fused.hip, csrc/rtm.hip) at and past its range: the
+  * the 64-bit fixed-point loss hand-off of the folded scoring (csrc/mlp_fused.hip, csrc/rtm_score.hip) at and past its range: the
     largest workgroup partial just under the limit (at 1, 33 and 263 workgroups: 2^20 and 2^19 units), past it (the loss is
     +inf, never a finite number), a NaN operand — and after each of the last two a benign step through the same module, which
     must match the oracle again: the poison word and the arrival count are cleared per step.
