@@ -91,17 +91,27 @@ def rtm_forward(P, args, batch, neg_word_idxs, vocab_size, review_count, trainin
             pidx = batch.pos_prod_rword_idxs.view(B * R, -1)
             pos_rev = pvc_para_vector(P, pidx, word_pad, tm(tuple(pidx.shape), 'pos'))
             neg_idx = batch.neg_prod_rword_idxs.view(B * K * R, -1)
-        neg_rev = pvc_para_vector(P, neg_idx, word_pad, tm(tuple(neg_idx.shape), 'neg')).view(B, K, R, d)
+        neg_flat = pvc_para_vector(P, neg_idx, word_pad, tm(tuple(neg_idx.shape), 'neg'))
+        if keep is not None and keep.get('leaf_means'):
+            # a caller that holds the word table constant (full size: nothing table-sized is saved) still gets
+            # d loss / d mean of every review slot: the means become leaves
+            pos_rev, neg_flat = (t.detach().requires_grad_(True) for t in (pos_rev, neg_flat))
+        neg_rev = neg_flat.view(B, K, R, d)
+        means = (pos_rev, neg_flat)
     elif enc_name in ('fs', 'avg'):
         # FSEncoder / AVGEncoder over the review words with the BATCH's word masks (ps_model.py:301-305,
         # text_encoder.py:32-40 / :76-83): masked mean -> dropout (-> tanh(f_W . + b)); no further dropout_layer, no PV loss
+        means = []
+
         def enc(idx, mask, which):
             n = idx.shape[0] * idx.shape[1] if idx.dim() == 3 else idx.shape[0]
             idx2, m2 = idx.reshape(-1, idx.shape[-1]), mask.reshape(-1, mask.shape[-1]).bool()
             out = []
             for lo in range(0, idx2.shape[0], 4096):
                 out.append(vector_mean(P['word_embeddings.weight'][idx2[lo:lo + 4096]], m2[lo:lo + 4096]))
-            mean = drop(torch.cat(out, 0), which, 0)
+            mean = torch.cat(out, 0)
+            means.append(mean)
+            mean = drop(mean, which, 0)
             if enc_name == 'fs':
                 mean = torch.tanh(F.linear(mean, P['review_encoder.f_W.weight'], P['review_encoder.f_W.bias']))
             return mean
@@ -153,6 +163,10 @@ def rtm_forward(P, args, batch, neg_word_idxs, vocab_size, review_count, trainin
         keep.update(query_emb=query_emb, pos_rev=pos_rev, neg_rev=neg_rev, scores=scores,
                     enc_pos=top_p[:, 0, :], enc_neg=top_n[:, 0, :].view(B, K, d),
                     pos_seq=pos_seq, neg_seq=neg_seq, pos_mask=pos_mask, neg_mask=neg_mask, weight=weight)
+        if enc_name != 'pv':
+            # the word means the sequence's review slots are made of, WITH their graph: d loss / d mean of a slot, divided by
+            # the slot's word count, is what one occurrence of a word in that slot adds to the word's row (tests/rtm_word_rows.py)
+            keep.update(mean_pos=means[0], mean_neg=means[1])
         if train_pv:
             keep.update(pv_scores=pv_scores, per_rev=per_rev)
     return loss, ps_loss, pv_loss

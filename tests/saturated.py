@@ -255,19 +255,25 @@ RTM_SEQS_PER_WG = 4      # rtm_score_kernel: a wave per sequence, four per workg
 RTM_FOLD_TOTAL = 134217728.0   # 2^27: a workgroup's partial times the grid stays below it
 
 
-def rtm_problem(d, heads, B, K, u_lim, i_lim, WL, encoder):
+def rtm_problem(d, heads, B, K, u_lim, i_lim, WL, encoder, V=1500, RC=900, words=None, train_pv=False, edit=None):
     """The harness's inputs, with the state dict of the module's own initialisation under torch.manual_seed(0) (built on the
-    CPU: the initialisation draws there whatever the device).  The global generator is put back."""
+    CPU: the initialisation draws there whatever the device).  The global generator is put back.
+    tests/rtm_word_rows.py's cases bring their own vocabulary and review count, their own review-word table (``words(rng, V,
+    RC, WL)`` -> int64 [RC, WL], review lengths cut with the pad word; the pad review is written here), the PV loss
+    (``train_pv``: its sampled words are drawn here, ``neg_words``) and ``edit(batch, rw)``, which changes the finished
+    batch in place."""
     from prodsearch_amd import ProductRanker, default_args, synth, rtm_data
-    V, RC = 1500, 900
     a = default_args(model_name='review_transformer', review_encoder_name=encoder, embedding_size=d, heads=heads,
                      ff_size=2 * d, inter_layers=1, neg_per_pos=K, dropout=0.0, corrupt_rate=0.0, lr=0.0005,
                      review_word_limit=WL, uprev_review_limit=u_lim, iprev_review_limit=i_lim)
     wd = synth.make_word_dists(V)
     rng = synth.rng_for(3)
-    rw = torch.from_numpy(rng.integers(0, V - 1, size=(RC, WL)))
-    lens = torch.from_numpy(rng.integers(1, WL + 1, size=RC))
-    rw[torch.arange(WL)[None, :] >= lens[:, None]] = V - 1
+    if words is None:
+        rw = torch.from_numpy(rng.integers(0, V - 1, size=(RC, WL)))
+        lens = torch.from_numpy(rng.integers(1, WL + 1, size=RC))
+        rw[torch.arange(WL)[None, :] >= lens[:, None]] = V - 1
+    else:
+        rw = words(rng, V, RC, WL)
     rw[-1] = V - 1
     state = torch.get_rng_state()
     try:
@@ -276,13 +282,21 @@ def rtm_problem(d, heads, B, K, u_lim, i_lim, WL, encoder):
     finally:
         torch.set_rng_state(state)
     sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    batch = rtm_data.make_rtm_batch(21, B, K, RC, V, rw, Q=5, u_lim=u_lim, i_lim=i_lim, W=1, train_pv=False,
+    batch = rtm_data.make_rtm_batch(21, B, K, RC, V, rw, Q=5, u_lim=u_lim, i_lim=i_lim, W=1, train_pv=train_pv,
                                     encoder=encoder, word_dists=wd)
-    return types.SimpleNamespace(a=a, wd=wd, rw=rw, sd=sd, batch=batch, V=V, RC=RC, B=B, K=K)
+    neg_words = None
+    if train_pv:         # the PV loss's sampled words, [B R, W K] with W = 1 (PV.py:57 draws them from word_dists; pad excluded)
+        neg_words = torch.from_numpy(synth.rng_for(22).integers(0, V - 1, size=(B * (u_lim + i_lim), K)))
+    if edit is not None:
+        edit(batch, rw)
+    return types.SimpleNamespace(a=a, wd=wd, rw=rw, sd=sd, batch=batch, V=V, RC=RC, B=B, K=K, train_pv=train_pv,
+                                 neg_words=neg_words)
 
 
 def rtm_oracle_step(p, sd, f64):
-    """Loss, the [B, K + 1] logits and every gradient of oracle.rtm on ``sd`` in float64 or float32, and ``keep``."""
+    """Loss, the [B, K + 1] logits and every gradient of oracle.rtm on ``sd`` in float64 or float32, and ``keep``.  With a
+    word-mean review encoder also ``slot_grads``: d loss / d word mean of the positives' [B R, d] and the negatives'
+    [B K R, d] review slots."""
     from oracle import rtm as ortm
 
     def run():
@@ -291,10 +305,16 @@ def rtm_oracle_step(p, sd, f64):
             v = v.double() if (f64 and v.dtype.is_floating_point) else v.clone()
             P[k] = v.requires_grad_(True) if (v.dtype.is_floating_point and not k.endswith('pos_emb.pe')) else v
         keep = {}
-        loss, _, _ = ortm.rtm_forward(P, p.a, p.batch, None, p.V, p.RC, training=True, train_pv=False, keep=keep)
+        tpv = bool(getattr(p, 'train_pv', False))
+        loss, _, _ = ortm.rtm_forward(P, p.a, p.batch, getattr(p, 'neg_words', None), p.V, p.RC, training=True, train_pv=tpv,
+                                      keep=keep)
         names = [k for k, v in P.items() if torch.is_tensor(v) and v.requires_grad]
-        gs = torch.autograd.grad(loss, [P[k] for k in names], allow_unused=True)
-        return dict(loss=loss.detach(), logits=keep['scores'].detach(), grads=dict(zip(names, gs)), keep=keep)
+        slots = [keep[k] for k in ('mean_pos', 'mean_neg') if k in keep]
+        gs = torch.autograd.grad(loss, [P[k] for k in names] + slots, allow_unused=True)
+        out = dict(loss=loss.detach(), logits=keep['scores'].detach(), grads=dict(zip(names, gs)), keep=keep)
+        if slots:
+            out['slot_grads'] = tuple(gs[len(names):])
+        return out
     return oracle_f64(run) if f64 else run()
 
 

@@ -65,7 +65,8 @@ def _check_forward(a, sd, m, batch, loss, keep, oloss):
 @pytest.mark.parametrize('encoder', ['pvc', 'pv'])
 def test_rtm_full_size_matches_the_oracle(encoder):
     """dropout 0, corrupt 0: loss, logits, every forward stage, the gradients of every small tensor (oracle autograd with
-    the word table held constant, so nothing table-sized is saved), the touched word / review rows bit-exactly."""
+    the word table held constant, so nothing table-sized is saved), the touched word / review rows bit-exactly and, pvc,
+    the word gradient's values on a sample of rows."""
     from oracle import rtm as ortm
     a, sd, m, batch = _setup(encoder)
     loss = m(batch.to('cuda'), train_pv=False)
@@ -107,6 +108,20 @@ def test_rtm_full_size_matches_the_oracle(encoder):
     words = np.setdiff1d(np.unique(words), [V - 1])
     got_w = torch.nonzero(m.word_embeddings.weight.grad.ne(0).any(1)).flatten().cpu().numpy()
     assert np.array_equal(got_w, words)
+    if encoder == 'pvc':
+        # the word gradient's VALUES on 128 rows — the 64 most frequent words of the batch and its 64 rarest, none in a query —
+        # each on its own scale (tests/rtm_word_rows.py): reference rows summed in float64 from the float64 oracle's gradient
+        # on the review slots' word means, the table held constant
+        import types
+        import rtm_word_rows as W
+        p = types.SimpleNamespace(a=a, batch=batch, V=V, RC=RC, B=B, K=K, train_pv=False)
+        rows = W.fullsize_sample(p)
+        dec = W.decompose(p, W.slot_grads_with_the_table_constant(p, sd, True), rows=rows)
+        limit = max(8.0 * W.YARDSTICK_FULLSIZE, W.FLOOR)
+        grad = m.word_embeddings.weight.grad[rows.cuda()].cpu()
+        print('figures: full size, %d rows of %d .. %d occurrences: worst err_w %.3e bound %.3e'
+              % (rows.numel(), int(dec.count.min()), int(dec.count.max()), float(W.row_errors(grad, dec).max()), limit))
+        W.compare(grad, dec, limit, what='full size pvc (HIST)')
 
 
 def test_rtm_full_size_token_corruption_follows_the_philox_stream():

@@ -57,6 +57,33 @@ def test_rtm_wide_and_ragged_shapes_match_the_oracle(d, heads, B, K, u_lim, i_li
         checked += 1
     assert checked >= 16
     m.check_index_errors() if hasattr(m, 'check_index_errors') else None
+    # bit-exact index work: the rows of the tables that received a gradient are the rows the batch addresses
+    qw = batch.query_word_idxs.reshape(-1)
+    pos_ok, neg_ok = batch.pos_prod_ridxs.ne(RC - 1), batch.neg_prod_ridxs.ne(RC - 1)
+    if encoder == 'pv':
+        words = qw
+        revs = torch.unique(torch.cat([batch.pos_prod_ridxs[pos_ok], batch.neg_prod_ridxs[neg_ok]]))
+        got_r = torch.nonzero(m.review_encoder.review_embeddings.weight.grad.ne(0).any(1)).flatten().cpu()
+        assert torch.equal(got_r, revs)
+    else:
+        pw, nw = batch.pos_prod_rword_idxs[pos_ok], batch.neg_prod_rword_idxs[neg_ok]
+        if encoder != 'pvc':                          # fs / avg count a word by the batch's mask
+            pw, nw = pw[batch.pos_prod_rword_masks[pos_ok].bool()], nw[batch.neg_prod_rword_masks[neg_ok].bool()]
+        words = torch.cat([qw, pw.reshape(-1), nw.reshape(-1)])
+    words = torch.unique(words)
+    words = words[words.ne(V - 1)]
+    got_w = torch.nonzero(m.word_embeddings.weight.grad.ne(0).any(1)).flatten().cpu()
+    assert torch.equal(got_w, words)
+    if encoder != 'pv':
+        # the word table row by row on each row's own scale (tests/rtm_word_rows.py), against the float64 oracle of the same
+        # inputs: saturated.rtm_problem builds them exactly as above
+        import rtm_word_rows as W
+        name = 'shape_d%d_%s' % (d, encoder)
+        p, r64, dec = W.reference(name)
+        assert torch.equal(p.sd['word_embeddings.weight'], sd['word_embeddings.weight'])
+        assert torch.equal(p.batch.neg_prod_rword_idxs, batch.neg_prod_rword_idxs) and torch.equal(W.addressed_words(p), words)
+        worst = W.compare(m.word_embeddings.weight.grad, dec, W.bound(name), words, what=name)
+        print('figures: %s worst err_w %.3e bound %.3e' % (name, worst, W.bound(name)))
 
 
 def test_second_backward_over_the_same_forward_accumulates_the_same_gradient():
