@@ -62,8 +62,11 @@ class TorchDropout(object):
 def query_encode(P, args, query_word_idxs, word_pad_idx, drop, keep=None):
     """``word_embeddings`` gather + ``FSEncoder.forward`` (text_encoder.py:32-40) or
     ``AVGEncoder.forward`` (:76-83); call site item_transformer.py:449-450.
-    ``keep['fs_pre']``: the FS projection's pre-activation (bookkeeping only)."""
+    ``keep['fs_pre']``: the FS projection's pre-activation; ``keep['query_word_emb']``: the [B, Q, d] gather (bookkeeping
+    only)."""
     emb = P['word_embeddings.weight'][query_word_idxs]
+    if keep is not None:
+        keep['query_word_emb'] = emb
     mean = vector_mean(emb, query_word_idxs.ne(word_pad_idx))
     mean_d = drop(mean, 'fs', 0)
     if args.query_encoder_name == 'fs':
@@ -170,14 +173,16 @@ def item_to_words(P, target_prod_idxs, pos_iword_idxs, neg_word_idxs, word_pad_i
     wneg = P['word_embeddings.weight'][neg_word_idxs.view(B, -1)]
     out_pos = torch.bmm(wpos, prod.unsqueeze(2))
     out_neg = torch.bmm(wneg, prod.unsqueeze(2)).view(B, W, -1)
-    out_pos = out_pos + P['word_bias'][pos_iword_idxs.view(-1)].view(B, W, 1)
-    out_neg = out_neg + P['word_bias'][neg_word_idxs.reshape(-1)].view(B, W, -1)
+    bpos = P['word_bias'][pos_iword_idxs.view(-1)]
+    bneg = P['word_bias'][neg_word_idxs.reshape(-1)]
+    out_pos = out_pos + bpos.view(B, W, 1)
+    out_neg = out_neg + bneg.view(B, W, -1)
     scores = torch.cat((out_pos, out_neg), dim=-1)
     target = torch.cat((torch.ones_like(out_pos), torch.zeros_like(out_neg)), dim=-1)
     loss = F.binary_cross_entropy_with_logits(scores, target, reduction='none').sum(-1)
     loss = vector_mean(loss.unsqueeze(-1), pos_iword_idxs.ne(word_pad_idx))
-    if keep is not None:
-        keep['word_scores'] = scores
+    if keep is not None:      # the gathered rows, for the gradient of every occurrence (tests/tem_table_rows.py)
+        keep.update(word_scores=scores, pv_prod=prod, pv_wpos=wpos, pv_wneg=wneg, pv_bpos=bpos, pv_bneg=bneg)
     return loss.mean()
 
 
@@ -213,23 +218,27 @@ def tem_forward(P, args, batch, neg_item_idxs, neg_word_idxs, vocab_size, produc
                              u_emb.unsqueeze(1).expand(-1, K, -1, -1)], dim=2)      # :473-476
         neg_mask = seq_mask.unsqueeze(1).expand(-1, K, -1)                          # :458-460
         k1 = {} if keep is not None else None
-        top_n = encoder_encode(P, args, neg_seq.reshape(B * K, L + 1, d),
-                               neg_mask.reshape(B * K, L + 1), pe, drop, 1, k1)     # :486-491
+        neg_in = neg_seq.reshape(B * K, L + 1, d)
+        top_n = encoder_encode(P, args, neg_in, neg_mask.reshape(B * K, L + 1), pe, drop, 1, k1)     # :486-491
         if keep is not None:
             keep['neg'] = k1           # the negatives' encode, as the positives' at the top level (bookkeeping only)
+            keep['neg_seq'] = neg_in
         neg_out = top_n[:, out_pos, :].view(B, K, d)
     else:
         neg_out = pos_out.unsqueeze(1).expand(-1, K, -1)
     neg_scores = (neg_out * neg_emb).sum(-1)                                        # :493-494
     if args.sim_func == 'bias_product':                                             # :495-499
-        pos_scores = pos_scores + P['product_bias'][tgt]
-        neg_scores = neg_scores + P['product_bias'][neg_item_idxs]
+        target_bias, neg_bias = P['product_bias'][tgt], P['product_bias'][neg_item_idxs]
+        pos_scores = pos_scores + target_bias
+        neg_scores = neg_scores + neg_bias
+        if keep is not None:
+            keep.update(target_bias=target_bias, neg_bias=neg_bias)
     ps_loss = bce_rank_loss(pos_scores, neg_scores, K if args.pos_weight else 1)     # :500-514
     item_loss = item_to_words(P, tgt, batch.pos_iword_idxs, neg_word_idxs, word_pad, keep)  # :515
     if keep is not None:
         keep.update(k0)
         keep.update(query_mean=qmean, query_emb=query_emb, seq_mask=seq_mask, enc=pos_out,
-                    pos_scores=pos_scores, neg_scores=neg_scores)
+                    pos_scores=pos_scores, neg_scores=neg_scores, target_emb=target_emb, neg_emb=neg_emb, pos_seq=pos_seq)
     return ps_loss + item_loss, ps_loss, item_loss
 
 
@@ -277,13 +286,16 @@ def qem_forward(P, args, batch, neg_item_idxs, neg_word_idxs, vocab_size, produc
     pos_scores = (query_emb * target_emb).sum(-1)
     neg_scores = (query_emb.unsqueeze(1) * neg_emb).sum(-1)
     if args.sim_func == 'bias_product':
-        pos_scores = pos_scores + P['product_bias'][tgt]
-        neg_scores = neg_scores + P['product_bias'][neg_item_idxs]
+        target_bias, neg_bias = P['product_bias'][tgt], P['product_bias'][neg_item_idxs]
+        pos_scores = pos_scores + target_bias
+        neg_scores = neg_scores + neg_bias
+        if keep is not None:
+            keep.update(target_bias=target_bias, neg_bias=neg_bias)
     ps_loss = bce_rank_loss(pos_scores, neg_scores, K if args.pos_weight else 1)
     item_loss = item_to_words(P, tgt, batch.pos_iword_idxs, neg_word_idxs, word_pad, keep)
     if keep is not None:
         keep.update(query_mean=qmean, query_emb=query_emb, enc=query_emb,
-                    pos_scores=pos_scores, neg_scores=neg_scores)
+                    pos_scores=pos_scores, neg_scores=neg_scores, target_emb=target_emb, neg_emb=neg_emb)
     return ps_loss + item_loss, ps_loss, item_loss
 
 

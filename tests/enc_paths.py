@@ -109,7 +109,14 @@ NEW_ROWS = [
     row('l2_d512', 6, 4, 20, 512, [GEN, GEN], '', F=1024, layers=2),         # the generic form as the last of several layers (S = 21, as d512_drop)
     row('mf1008', 48, 20, 9, 128, [KVQ], FUSED_D128, fuse_bwd_min=PS_FUSE_BWD_MIN),
     row('mf1029', 49, 20, 9, 128, [KVQ], C2_FLAGS, fuse_bwd_min=PS_FUSE_BWD_MIN),
+    # ---- tests/tem_table_rows.py's shapes that no row above has
+    row('avg_d96', 50, 20, 9, 96, [SQ1], 'RL LI PR', F=192, query_encoder_name='avg'),        # d = 96: nothing fused, no wf
+    row('avg_d64_nodrop', 6, 4, 20, 64, [W1], 'RL QF LI', H=4, F=128, dropout=0.0, query_encoder_name='avg'),
+    row('heavy_nodrop', 50, 20, 9, 128, [W1], 'RL FF QF LI', dropout=0.0),                    # e_50_20_9 without replicas
 ]
+for _q in (33, 64, 65, 70):      # queries of up to Q words at 30 replica rows: the plan does not read Q
+    NEW_ROWS.append(row('q%d_fs' % _q, 6, 4, 9, 128, [KVQ], FUSED_D128, Q=_q))
+    NEW_ROWS.append(row('q%d_avg' % _q, 6, 4, 9, 128, [KVQ], 'RL FF FS QF LI', Q=_q, query_encoder_name='avg'))
 
 ALL_ROWS = EDGE_ROWS + list(WIDE_ROWS.values()) + list(OPTION_ROWS.values()) + list(PARTIAL_TILE_ROWS.values()) + NEW_ROWS
 assert len({r['name'] for r in ALL_ROWS}) == len(ALL_ROWS)

@@ -109,8 +109,9 @@ def oracle_f64(fn):
 
 
 # ------------------------------------------------------------------------------------------------- item transformer / QEM
-def problem(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, **over):
-    """The inputs of test_gpu_tem_options.check_against_oracle for the same arguments, without a device."""
+def problem(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, edit=None, **over):
+    """The inputs of test_gpu_tem_options.check_against_oracle for the same arguments, without a device.  ``edit(p)`` changes
+    the finished problem in place (tests/tem_table_rows.py: refilled queries, a heavy item, a pretrained word table)."""
     from prodsearch_amd import default_args, synth
     kw = dict(model_name='item_transformer', embedding_size=128, heads=8, ff_size=256, inter_layers=1, neg_per_pos=K,
               dropout=0.1, uprev_review_limit=L, pv_window_size=W)
@@ -120,13 +121,22 @@ def problem(B, K, L, Q, W=1, zero_hist=0.2, P_=700, V=900, **over):
     sd = synth.make_state_dict(synth.tem_param_shapes(a, V, P_), 7, {'product_emb.weight': P_, 'hist_product_emb.weight': P_})
     batch = synth.make_tem_batch(11, B, P_, V, Q=Q, L=L, W=W, C=9, word_dists=wd, zero_hist_frac=zero_hist)
     ni, nw = synth.sample_negatives(12, B, K, W, P_, wd)
-    return types.SimpleNamespace(a=a, wd=wd, sd=sd, batch=batch, ni=ni, nw=nw, B=B, K=K, L=L, W=W, P_=P_, V=V,
-                                 qem=a.model_name == 'QEM')
+    p = types.SimpleNamespace(a=a, wd=wd, sd=sd, batch=batch, ni=ni, nw=nw, B=B, K=K, L=L, W=W, P_=P_, V=V,
+                              qem=a.model_name == 'QEM')
+    if edit is not None:
+        edit(p)
+    return p
 
 
-def oracle_step(p, sd, f64, step=1, seed=666, want_eval=True):
+OCC_KEYS = ('query_word_emb', 'target_emb', 'neg_emb', 'target_bias', 'neg_bias', 'pos_seq', 'neg_seq',
+            'pv_prod', 'pv_wpos', 'pv_wneg', 'pv_bpos', 'pv_bneg')
+
+
+def oracle_step(p, sd, f64, step=1, seed=666, want_eval=True, want_occ=False):
     """One training step (and the eval scores) of oracle.tem on ``sd`` in float64 or float32, replicated with the product's
-    Philox masks of training step ``step``: loss, the [B, K + 1] logits, every gradient, eval scores, and ``keep``."""
+    Philox masks of training step ``step``: loss, the [B, K + 1] logits, every gradient, eval scores, and ``keep``.
+    ``want_occ``: also ``occ``, d loss / d of every tensor the oracle gathers from a table (OCC_KEYS, those the model has):
+    one row of it is one occurrence's contribution to its table row (tests/tem_table_rows.py)."""
     from oracle import tem as otem, philox
     a = p.a
 
@@ -142,8 +152,12 @@ def oracle_step(p, sd, f64, step=1, seed=666, want_eval=True):
         else:
             loss, _, _ = otem.tem_forward(Pm, a, p.batch, p.ni, p.nw, p.V, p.P_, training=True, replicate=drop is not None,
                                           drop=drop, keep=keep)
+        occ = None
+        if want_occ:
+            names = [k for k in OCC_KEYS if k in keep]
+            occ = dict(zip(names, torch.autograd.grad(loss, [keep[k] for k in names], retain_graph=True)))
         grads = otem.grads_of(loss, Pm, otem.tem_pad_rows(a, p.V, p.P_))
-        out = dict(loss=loss.detach(), grads=grads, keep=keep,
+        out = dict(loss=loss.detach(), grads=grads, keep=keep, occ=occ,
                    logits=torch.cat([keep['pos_scores'].detach()[:, None], keep['neg_scores'].detach()], 1))
         if want_eval:
             with torch.no_grad():
