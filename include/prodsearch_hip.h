@@ -572,6 +572,45 @@ int ps_rtm_score(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmB
 int ps_rtm_review_embeddings(const PsRtmDesc* desc, const PsRtmTensors* params, const int64_t* review_words,
                              float* scratch, float* out, ps_stream_t stream);
 
+/* ------------------------------------------------------------------ RTM: the whole catalogue in one pass
+ * What Trainer.test computes for the review transformer with test_candi_size < 1 (trainer.py:141-143, 189-226), without running
+ * the encoder over every (entry, candidate) sequence: with ONE encoder layer a key / value row is linear in its token, every
+ * per-review term depends on the review id alone (a review has one author and one item), and only position 0 is consumed —
+ * so the reviews are projected once per evaluation (ps_rtm_rank_index), K / V / Q and the softmax partial over {query, the
+ * user's reviews} once per entry, and per (entry, item) pair there is the softmax partial over the item's reviews, the merge
+ * and the position-0 tail.  desc: B = entries per call, R = --uprev_review_limit + --iprev_review_limit (longest sequence;
+ * item reviews past it are cut, as the loader cuts), Q, d, H, F, n_layers, review_count, vocab_size, the encoders and the use_*
+ * flags; K, W, WL, C, training, dropout are not read.
+ * Refused (error return, message naming the flag): n_layers != 1 (deeper encoders need every position of layer 0);
+ * seq_review_test (do_seq_review_test and not train_review_only: the item lists then depend on the entry); fs / avg review
+ * encoders with fix_emb. */
+typedef struct PsRtmRankShape {
+  int64_t n_items;           /* P: rows of item_ridxs, catalogue ids 0..P-1                                      */
+  int64_t review_u_p_rows;   /* rows of review_u_p (reviews past them get no user / item row)                    */
+  int32_t I;                 /* item_ridxs [P, I]: the item's reviews, then the pad id review_count-1            */
+  int32_t U;                 /* u_ridxs [B, U]: the user's reviews, then the pad id                              */
+  int32_t seq_review_test;   /* the run has do_seq_review_test and not train_review_only: refused                */
+  int32_t fix_emb;           /* the run has fix_emb (refused with the fs / avg review encoders)                  */
+} PsRtmRankShape;
+/* floats of the projection ps_rtm_rank_index writes; -1 with ps_last_error() set: refused / bad sizes */
+int64_t ps_rtm_rank_index_floats(const PsRtmDesc* desc, const PsRtmRankShape* shape);
+/* Once per evaluation: KR / VR [review_count, d] = Wk / Wv . (review_embeddings[r] (+ user_emb[u_r]) (+ product_emb[i_r])) and the
+ * [segment][position] key / value tables Wk / Wv . (seg + pe) + b.  review_embeddings: the table ProductRanker.test indexes;
+ * review_u_p [review_u_p_rows, 2] (author, item): read only with use_user_emb / use_item_emb, else NULL.  The result is
+ * stale once a weight or a table changes. */
+int ps_rtm_rank_index(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params,
+                      const float* review_embeddings, const int64_t* review_u_p, float* index_out, ps_stream_t stream);
+/* bytes of scratch for ps_rtm_rank_all with `items_per_pass` items scored per pass (<= 0: the default, 32768 pairs);
+ * -1: refused / bad sizes.  ps_rtm_rank_all sizes its passes from the scratch it is given: the most items that fit. */
+int64_t ps_rtm_rank_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t items_per_pass);
+/* item_ridxs [P, I]; query_word_idxs [B, Q]; u_ridxs [B, U]; target_prod_idxs [B] (NULL: no rank).  top_idx / top_score
+ * [B, topk], rank [B]: the semantics of ps_rank_all (score desc, id asc; rank 1-based, 0: the target is not an item;
+ * topk <= 256; unfilled slots -1 / -inf).  scores_out (optional) [B, P] dense.  scratch: 256-byte aligned. */
+int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
+                    const int64_t* item_ridxs, const int64_t* query_word_idxs, const int64_t* u_ridxs,
+                    const int64_t* target_prod_idxs, int32_t topk, int64_t* top_idx, float* top_score, int32_t* rank,
+                    float* scores_out, void* scratch, int64_t scratch_bytes, ps_stream_t stream);
+
 /* Host evaluation of the dropout stream (tests pin oracle/philox.py to it): multiplier
  * (0 or 1/(1-p)) of element (row, col) of dropout site `site` at desc->seed/step/dropout. */
 float ps_dropout_mult_host(const PsTemDesc* desc, uint32_t site, uint32_t row, uint32_t col);

@@ -122,6 +122,12 @@ class PsRtmWsLayout(C.Structure):
 
 PS_RENC_PV, PS_RENC_PVC, PS_RENC_FS, PS_RENC_AVG = 0, 1, 2, 3
 
+
+class PsRtmRankShape(C.Structure):
+    _fields_ = [('n_items', C.c_int64), ('review_u_p_rows', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('I', 'U', 'seq_review_test', 'fix_emb')]
+
+
 # every symbol include/prodsearch_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     'ps_version': (C.c_char_p, []),
@@ -163,6 +169,12 @@ SYMBOLS = {
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     'ps_rtm_review_embeddings': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmTensors), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ps_rtm_rank_index_floats': (C.c_int64, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape)]),
+    'ps_rtm_rank_index': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.POINTER(PsRtmTensors), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ps_rtm_rank_scratch_bytes': (C.c_int64, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int32, C.c_int64]),
+    'ps_rtm_rank_all': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.POINTER(PsRtmTensors)] +
+                        [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
     'ps_sample_negatives': (C.c_int, [C.POINTER(PsTemDesc), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     'ps_build_alias_host': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

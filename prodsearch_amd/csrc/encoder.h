@@ -82,7 +82,15 @@ struct EncFwdOpts {
 };
 int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
                        const Ws& w, hipStream_t st, const EncFwdOpts& o);
-// Backward of the above: reads w.denc (grad wrt w.enc), accumulates parameter grads into G, writes w.dx.
+// The per-replica tail of layer i behind its attention, as enc_layers_forward runs it: Wo + residual -> FF LayerNorm -> W1 -> GELU
+// -> W2 + residual, reading l.ctx [l.M2, d] and the residual row (m / l.fan) * w.S + w.qpos of xin.  `fuse`: the one-kernel form of
+// the LAST layer (mlp_fused.hip: needs w.wsplit filled by an embed launch, d = 128), which also applies the final LayerNorm into
+// w.enc; otherwise the caller follows with enc_final_ln_forward.  Callers: the layer loop, and the review transformer's
+// full-catalogue ranking (rtm_rank.hip), whose "replicas" are the candidates of an entry.
+int enc_tail_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, int i, const float* xin, bool fuse,
+                     const ScoreArgs* fold_sc, hipStream_t st);
+int enc_final_ln_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, hipStream_t st);
+// Backward of enc_layers_forward: reads w.denc (grad wrt w.enc), accumulates parameter grads into G, writes w.dx.
 struct EncBwdIn {
   // the LayerNorm backwards park their column sums in w.lnpart and append to this list; the caller must hand it to a later
   // launch_embed_scatter (EmbedBwdArgs::fold).  nullptr: plain atomics

@@ -225,6 +225,64 @@ static AttnArgs attn_shape(const PsTemDesc& D, const Ws& w, int i, const int64_t
   return a;
 }
 
+// Layer i's per-replica tail behind its attention (encoder.h): reads l.ctx and the residual rows of xin.
+int enc_tail_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, int i, const float* xin, bool fuse,
+                     const ScoreArgs* fold_sc, hipStream_t st) {
+  const int d = D.d, S = w.S;
+  const LayerWs& l = w.layer[i];
+  const PsLayerTensors& Lp = P.layer[i];
+  if (fuse) {   // Wo + LN + W1 + GELU + W2 + final LN of the last layer in one kernel (mlp_fused.hip)
+    MlpFwdArgs m;
+    memset(&m, 0, sizeof(m));
+    m.M = l.M2; m.F = D.F; m.fan = l.fan; m.S = S; m.qpos = w.qpos;
+    m.ctx = ws + l.ctx; m.xin = xin;
+    m.wo = Lp.wo; m.bo = Lp.bo; m.g1 = Lp.ff_ln_g; m.be1 = Lp.ff_ln_b; m.w1 = Lp.w1; m.b1 = Lp.b1;
+    m.w2 = Lp.w2; m.b2 = Lp.b2; m.gf = P.final_ln_g; m.bef = P.final_ln_b;
+    m.drop_ctx = make_drop(D, PS_SITE_CTX(i)); m.drop_ff1 = make_drop(D, PS_SITE_FF1(i));
+    m.drop_ff2 = make_drop(D, PS_SITE_FF2(i));
+    m.y1 = ws + l.y1; m.ln1 = ws + l.ln1; m.st1 = ws + l.ff_stats; m.a1 = ws + l.a1; m.h1 = ws + l.h1;
+    m.y2 = ws + l.y2; m.stf = ws + w.fin_stats; m.enc = ws + w.enc;
+    if (fold_sc) { m.fold_score = 1; m.sc = *fold_sc; }
+    m.x3 = make_wsplit(D, P, ws, w);
+    return launch_mlp_fwd_fused(m, st);
+  }
+  {   // final_linear + dropout + residual (neural.py:228-231, transformer.py:56)
+    GemmProblem p = gp(ws + l.ctx, d, 0, Lp.wo, d, 0, ws + l.y1, d, l.M2, d, d);
+    p.bias = Lp.bo; p.drop = make_drop(D, PS_SITE_CTX(i));
+    p.res.mode = RES_GATHER; p.res.ptr = xin; p.res.ld = d; p.res.Sq = l.Sq; p.res.fan = l.fan; p.res.S = S;
+    p.res.qpos = w.qpos; res_finish(p.res);
+    TRY(run1(p, st));
+  }
+  {   // PositionwiseFeedForward (neural.py:30-33)
+    LnFwdArgs n = {ws + l.y1, d, ws + l.ln1, d, ws + l.ff_stats, Lp.ff_ln_g, Lp.ff_ln_b, l.M2, d, 1e-6f};
+    TRY(launch_ln_fwd(n, st));
+    GemmProblem p1 = gp(ws + l.ln1, d, 0, Lp.w1, d, 0, ws + l.h1, D.F, l.M2, D.F, d);
+    p1.bias = Lp.b1; p1.aux_out = ws + l.a1; p1.act = ACT_GELU; p1.drop = make_drop(D, PS_SITE_FF1(i));
+    TRY(run1(p1, st));
+    GemmProblem p2 = gp(ws + l.h1, D.F, 0, Lp.w2, D.F, 0, ws + l.y2, d, l.M2, d, D.F);
+    p2.bias = Lp.b2; p2.drop = make_drop(D, PS_SITE_FF2(i));
+    p2.res.mode = RES_DIRECT; p2.res.ptr = ws + l.y1; p2.res.ld = d;
+    TRY(run1(p2, st));
+  }
+  return PS_OK;
+}
+
+// final LayerNorm (transformer.py:86) on the consumed position only
+int enc_final_ln_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, hipStream_t st) {
+  const int d = D.d, S = w.S, NL = D.n_layers;
+  PS_REQUIRE(P.final_ln_g && P.final_ln_b, "forward: null final LayerNorm");
+  LnFwdArgs f;
+  if (NL > 0) {
+    const LayerWs& l = w.layer[NL - 1];
+    f = LnFwdArgs{ws + l.y2, d, ws + w.enc, d, ws + w.fin_stats, P.final_ln_g, P.final_ln_b, w.Mf, d, 1e-6f};
+  } else {
+    f = LnFwdArgs{ws + w.x + (size_t)w.qpos * d, S * d, ws + w.enc, d, ws + w.fin_stats, P.final_ln_g,
+                  P.final_ln_b, D.B, d, 1e-6f};
+  }
+  TRY(launch_ln_fwd(f, st));
+  return PS_OK;
+}
+
 int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
                        const Ws& w, hipStream_t st, const EncFwdOpts& o) {
   const int d = D.d, S = w.S, NL = D.n_layers;
@@ -285,55 +343,11 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
     }
     const bool fuse = pl.fwd_fuse_last && i == NL - 1;
     PS_REQUIRE(!o.fold_sc || fuse || i != NL - 1, "forward: folded scoring without the fused last layer");   // (earlier layers: never fused)
-    if (fuse) {   // Wo + LN + W1 + GELU + W2 + final LN of the last layer in one kernel (mlp_fused.hip)
-      MlpFwdArgs m;
-      memset(&m, 0, sizeof(m));
-      m.M = l.M2; m.F = D.F; m.fan = l.fan; m.S = S; m.qpos = w.qpos;
-      m.ctx = ws + l.ctx; m.xin = xin;
-      m.wo = Lp.wo; m.bo = Lp.bo; m.g1 = Lp.ff_ln_g; m.be1 = Lp.ff_ln_b; m.w1 = Lp.w1; m.b1 = Lp.b1;
-      m.w2 = Lp.w2; m.b2 = Lp.b2; m.gf = P.final_ln_g; m.bef = P.final_ln_b;
-      m.drop_ctx = make_drop(D, PS_SITE_CTX(i)); m.drop_ff1 = make_drop(D, PS_SITE_FF1(i));
-      m.drop_ff2 = make_drop(D, PS_SITE_FF2(i));
-      m.y1 = ws + l.y1; m.ln1 = ws + l.ln1; m.st1 = ws + l.ff_stats; m.a1 = ws + l.a1; m.h1 = ws + l.h1;
-      m.y2 = ws + l.y2; m.stf = ws + w.fin_stats; m.enc = ws + w.enc;
-      if (o.fold_sc) { m.fold_score = 1; m.sc = *o.fold_sc; }
-      m.x3 = make_wsplit(D, P, ws, w);
-      TRY(launch_mlp_fwd_fused(m, st));
-      tk.fwd_fuse_last = 1; tk.fold_score = m.fold_score;
-      continue;
-    }
-    {   // final_linear + dropout + residual (neural.py:228-231, transformer.py:56)
-      GemmProblem p = gp(ws + l.ctx, d, 0, Lp.wo, d, 0, ws + l.y1, d, l.M2, d, d);
-      p.bias = Lp.bo; p.drop = make_drop(D, PS_SITE_CTX(i));
-      p.res.mode = RES_GATHER; p.res.ptr = xin; p.res.ld = d; p.res.Sq = l.Sq; p.res.fan = l.fan; p.res.S = S;
-      p.res.qpos = w.qpos; res_finish(p.res);
-      TRY(run1(p, st));
-    }
-    {   // PositionwiseFeedForward (neural.py:30-33)
-      LnFwdArgs n = {ws + l.y1, d, ws + l.ln1, d, ws + l.ff_stats, Lp.ff_ln_g, Lp.ff_ln_b, l.M2, d, 1e-6f};
-      TRY(launch_ln_fwd(n, st));
-      GemmProblem p1 = gp(ws + l.ln1, d, 0, Lp.w1, d, 0, ws + l.h1, D.F, l.M2, D.F, d);
-      p1.bias = Lp.b1; p1.aux_out = ws + l.a1; p1.act = ACT_GELU; p1.drop = make_drop(D, PS_SITE_FF1(i));
-      TRY(run1(p1, st));
-      GemmProblem p2 = gp(ws + l.h1, D.F, 0, Lp.w2, D.F, 0, ws + l.y2, d, l.M2, d, D.F);
-      p2.bias = Lp.b2; p2.drop = make_drop(D, PS_SITE_FF2(i));
-      p2.res.mode = RES_DIRECT; p2.res.ptr = ws + l.y1; p2.res.ld = d;
-      TRY(run1(p2, st));
-    }
+    TRY(enc_tail_forward(D, P, ws, w, i, xin, fuse, fuse ? o.fold_sc : nullptr, st));
+    if (fuse) { tk.fwd_fuse_last = 1; tk.fold_score = o.fold_sc ? 1 : 0; }
   }
   if (pl.fwd_fuse_last) return PS_OK;
-  // final LayerNorm (transformer.py:86) on the consumed position only
-  PS_REQUIRE(P.final_ln_g && P.final_ln_b, "forward: null final LayerNorm");
-  LnFwdArgs f;
-  if (NL > 0) {
-    const LayerWs& l = w.layer[NL - 1];
-    f = LnFwdArgs{ws + l.y2, d, ws + w.enc, d, ws + w.fin_stats, P.final_ln_g, P.final_ln_b, w.Mf, d, 1e-6f};
-  } else {
-    f = LnFwdArgs{ws + w.x + (size_t)w.qpos * d, S * d, ws + w.enc, d, ws + w.fin_stats, P.final_ln_g,
-                  P.final_ln_b, D.B, d, 1e-6f};
-  }
-  TRY(launch_ln_fwd(f, st));
-  return PS_OK;
+  return enc_final_ln_forward(D, P, ws, w, st);
 }
 
 // park the {dgamma, dbeta, colsum} column sums of one LN backward (see ColFoldList) when the caller collects them

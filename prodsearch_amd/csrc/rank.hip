@@ -10,6 +10,7 @@
 //                   rank counting against the target's score; repeated over the survivors until k remain, which a
 //                   256-wide bitonic network sorts by (score desc, index asc).
 #include "common.h"
+#include "rank.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -409,6 +410,113 @@ extern "C" int64_t ps_rank_scratch_bytes(int32_t B, int64_t n_rows, int32_t d, i
   return p.total;
 }
 
+// The selection over a dense score matrix, shared by ps_rank_all / ps_rank_shard (one call per scored panel) and by
+// rank_select_scores (rank.h: a score matrix somebody else computed).
+struct SelCtx {
+  float* cs[2]; int32_t* ci[2]; int32_t* cnt;      // survivor ping-pong buffers, per-chunk rank counts
+  int64_t chunks1;                                  // level-1 chunks over all panels
+  int B, topk;
+  int64_t* top_idx; float* top_score;
+  const int64_t* target; const float* stv; int32_t* rank;   // rank null: no rank counting
+  int64_t id_mul, id_add;
+  bool raw;                                         // rank receives the count of rows ahead (a shard), not 1 + count
+};
+// level 1 over the w scores per row of one panel (row stride ld) whose first column is table row r0
+static int select_panel(const SelCtx& c, const float* S, int64_t ld, int64_t w, int64_t r0, int64_t* chunk_off, hipStream_t st) {
+  SelArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src_score = S; a.src_idx = nullptr; a.src_ld = ld; a.n = (int)w; a.idx_base = r0;
+  a.out_score = c.cs[0]; a.out_idx = c.ci[0]; a.out_ld = c.chunks1 * c.topk; a.chunk_off = (int)*chunk_off; a.k = c.topk;
+  a.final = c.chunks1 == 1; a.top_idx = c.top_idx; a.top_score = c.top_score;
+  a.target = c.target; a.st = c.stv; a.rank = c.rank;
+  a.cnt = c.cnt; a.cnt_ld = c.chunks1;
+  a.id_mul = c.id_mul; a.id_add = c.id_add;
+  const int nch = (int)((w + SEL_CHUNK - 1) / SEL_CHUNK);
+  hipLaunchKernelGGL(select_kernel, dim3(nch, c.B), dim3(256), 0, st, a);
+  PS_LAUNCH_CHECK();
+  *chunk_off += nch;
+  return PS_OK;
+}
+// the target's rank from the per-chunk counts, then the survivors: [B, chunks*k] -> repeat until one chunk remains, which the
+// final pass sorts
+static int select_finish(const SelCtx& c, hipStream_t st) {
+  if (c.rank) {
+    hipLaunchKernelGGL(rank_sum_kernel, dim3(c.B), dim3(256), 0, st, c.cnt, c.chunks1, c.rank, c.raw ? 1 : 0);
+    PS_LAUNCH_CHECK();
+  }
+  if (c.chunks1 == 1) return PS_OK;
+  int cur = 0;
+  int64_t n = c.chunks1 * c.topk;
+  while (true) {
+    const int nch = (int)((n + SEL_CHUNK - 1) / SEL_CHUNK);
+    SelArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src_score = c.cs[cur]; a.src_idx = c.ci[cur]; a.src_ld = n; a.n = (int)n;
+    a.out_score = c.cs[cur ^ 1]; a.out_idx = c.ci[cur ^ 1]; a.out_ld = (int64_t)nch * c.topk; a.chunk_off = 0; a.k = c.topk;
+    a.final = nch == 1; a.top_idx = c.top_idx; a.top_score = c.top_score;
+    a.id_mul = c.id_mul; a.id_add = c.id_add;
+    hipLaunchKernelGGL(select_kernel, dim3(nch, c.B), dim3(256), 0, st, a);
+    PS_LAUNCH_CHECK();
+    if (nch == 1) break;
+    n = (int64_t)nch * c.topk;
+    cur ^= 1;
+  }
+  return PS_OK;
+}
+
+// ---- rank.h: top-k and the target's rank over a dense [B, n_rows] score matrix (the review transformer's full-catalogue pass)
+struct SelPlan { int64_t chunks1, off_st, off_c0s, off_c0i, off_c1s, off_c1i, off_cnt, total; };
+static void sel_plan(int B, int64_t n_rows, int k, SelPlan* p) {
+  p->chunks1 = (n_rows + SEL_CHUNK - 1) / SEL_CHUNK;
+  const int64_t cand0 = up((int64_t)B * p->chunks1 * k, 64);
+  const int64_t chunks2 = (p->chunks1 * k + SEL_CHUNK - 1) / SEL_CHUNK;
+  const int64_t cand1 = up((int64_t)B * chunks2 * k, 64);
+  int64_t cur = 0;
+  auto take = [&](int64_t bytes) { int64_t o = cur; cur += up(bytes, 256); return o; };
+  p->off_st = take((int64_t)B * 4);
+  p->off_c0s = take(cand0 * 4); p->off_c0i = take(cand0 * 4);
+  p->off_c1s = take(cand1 * 4); p->off_c1i = take(cand1 * 4);
+  p->off_cnt = take((int64_t)B * p->chunks1 * 4);
+  p->total = cur;
+}
+int64_t rank_select_scratch_bytes(int B, int64_t n_rows, int topk) {
+  if (B < 1 || n_rows < 1 || topk < 1 || topk > SEL_KMAX) return -1;
+  SelPlan p;
+  sel_plan(B, n_rows, topk, &p);
+  return p.total;
+}
+// the target's own entry of the score matrix (so it compares equal to itself) and the rank's start value
+__global__ void rank_pick_kernel(const float* S, int64_t ld, int B, const int64_t* target, int64_t n_rows, float* st, int32_t* rank) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int64_t r = target[b];
+  const bool ok = r >= 0 && r < n_rows;
+  st[b] = ok ? S[(size_t)b * ld + r] : INFINITY;
+  if (rank) rank[b] = ok ? 1 : 0;
+}
+int rank_select_scores(const float* S, int64_t ld, int B, int64_t n_rows, const int64_t* target, int topk, int64_t* top_idx,
+                       float* top_score, int32_t* rank, void* scratch, int64_t scratch_bytes, hipStream_t st) {
+  PS_REQUIRE(S && top_idx && top_score && scratch, "rank_select: null argument");
+  PS_REQUIRE(B >= 1 && n_rows >= 1 && n_rows < ((int64_t)1 << 31) && ld >= n_rows, "rank_select: bad sizes");
+  PS_REQUIRE(topk >= 1 && topk <= SEL_KMAX, "rank_select: topk must be 1..%d", SEL_KMAX);
+  PS_REQUIRE(!rank || target, "rank_select: rank needs target");
+  SelPlan p;
+  sel_plan(B, n_rows, topk, &p);
+  PS_REQUIRE(scratch_bytes >= p.total, "rank_select: scratch %lld < %lld bytes", (long long)scratch_bytes, (long long)p.total);
+  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rank_select: scratch must be 256-byte aligned");
+  char* base = (char*)scratch;
+  float* stv = (float*)(base + p.off_st);
+  if (target) {
+    hipLaunchKernelGGL(rank_pick_kernel, dim3((B + 255) / 256), dim3(256), 0, st, S, ld, B, target, n_rows, stv, rank);
+    PS_LAUNCH_CHECK();
+  }
+  SelCtx c = {{(float*)(base + p.off_c0s), (float*)(base + p.off_c1s)}, {(int32_t*)(base + p.off_c0i), (int32_t*)(base + p.off_c1i)},
+              (int32_t*)(base + p.off_cnt), p.chunks1, B, topk, top_idx, top_score, target, stv, target ? rank : nullptr, 1, 0, false};
+  int64_t chunk_off = 0;
+  TRY(select_panel(c, S, ld, n_rows, 0, &chunk_off, st));
+  return select_finish(c, st);
+}
+
 static int rank_all_impl(const float* q, int32_t B, int32_t d, const float* table, int64_t n_rows, const float* bias,
                          const int64_t* target, const float* ext_score, int64_t id_mul, int64_t id_add, int32_t topk,
                          int64_t* top_idx, float* top_score, int32_t* rank, void* scratch, int64_t scratch_bytes, ps_stream_t stream);
@@ -461,8 +569,8 @@ static int rank_all_impl(const float* q, int32_t B, int32_t d, const float* tabl
     hipLaunchKernelGGL(rank_diag_kernel, dim3((B + 255) / 256), dim3(256), 0, st, tt, B, bias, target, n_rows, stv, rank);
     PS_LAUNCH_CHECK();
   }
-  const bool single = p.chunks1 == 1;
-  const int64_t ld0 = p.chunks1 * topk;
+  SelCtx c = {{cs[0], cs[1]}, {ci[0], ci[1]}, cntb, p.chunks1, B, topk, top_idx, top_score, target, stv, target ? rank : nullptr,
+              id_mul, id_add, ext_score != nullptr};
   int64_t chunk_off = 0;
   for (int64_t pi = 0; pi < p.n_panels; ++pi) {
     const int64_t r0 = pi * p.panel;
@@ -475,40 +583,7 @@ static int rank_all_impl(const float* q, int32_t B, int32_t d, const float* tabl
       rc = ps_gemm_f32(q, d, 0, table + r0 * (int64_t)d, d, 0, S, (int)p.panel, B, (int)w, d, bias ? bias + r0 : nullptr,
                        1.f, 0, stream);
     if (rc) return rc;
-    SelArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src_score = S; a.src_idx = nullptr; a.src_ld = p.panel; a.n = (int)w; a.idx_base = r0;
-    a.out_score = cs[0]; a.out_idx = ci[0]; a.out_ld = ld0; a.chunk_off = (int)chunk_off; a.k = topk;
-    a.final = single; a.top_idx = top_idx; a.top_score = top_score;
-    a.target = target; a.st = stv; a.rank = target ? rank : nullptr;
-    a.cnt = cntb; a.cnt_ld = p.chunks1;
-    a.id_mul = id_mul; a.id_add = id_add;
-    const int nch = (int)((w + SEL_CHUNK - 1) / SEL_CHUNK);
-    hipLaunchKernelGGL(select_kernel, dim3(nch, B), dim3(256), 0, st, a);
-    PS_LAUNCH_CHECK();
-    chunk_off += nch;
+    TRY(select_panel(c, S, p.panel, w, r0, &chunk_off, st));
   }
-  if (target && rank) {
-    hipLaunchKernelGGL(rank_sum_kernel, dim3(B), dim3(256), 0, st, cntb, p.chunks1, rank, ext_score ? 1 : 0);
-    PS_LAUNCH_CHECK();
-  }
-  if (single) return PS_OK;
-  // survivors: [B, chunks*k] -> repeat until one chunk remains, which the final pass sorts
-  int cur = 0;
-  int64_t n = ld0;
-  while (true) {
-    const int nch = (int)((n + SEL_CHUNK - 1) / SEL_CHUNK);
-    SelArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src_score = cs[cur]; a.src_idx = ci[cur]; a.src_ld = n; a.n = (int)n;
-    a.out_score = cs[cur ^ 1]; a.out_idx = ci[cur ^ 1]; a.out_ld = (int64_t)nch * topk; a.chunk_off = 0; a.k = topk;
-    a.final = nch == 1; a.top_idx = top_idx; a.top_score = top_score;
-    a.id_mul = id_mul; a.id_add = id_add;
-    hipLaunchKernelGGL(select_kernel, dim3(nch, B), dim3(256), 0, st, a);
-    PS_LAUNCH_CHECK();
-    if (nch == 1) break;
-    n = (int64_t)nch * topk;
-    cur ^= 1;
-  }
-  return PS_OK;
+  return select_finish(c, st);
 }

@@ -116,6 +116,51 @@ def rank_all(model, batch, topk=100):
     return top_idx, top_score, rank
 
 
+def rank_all_rtm(model, index, batch, topk=100, items_per_pass=None, return_scores=False):
+    """The review transformer over the whole catalogue (``ps_rtm_rank_all``): what ``Trainer.test`` gets from
+    ``model.test`` over chunks of all products plus the host-side ranking, without encoding every (entry, candidate) sequence.
+    ``index`` = ``model.catalogue_index(item_ridxs, review_u_p)``; ``batch`` an entries-only batch (``ProdSearchRankBatch``:
+    ``query_word_idxs`` [B,Q], ``u_ridxs`` [B,U], ``target_prod_idxs`` [B], on the device).  ``items_per_pass``: bound the
+    workspace (default: 32768 pairs per pass).  -> (top_idx [B,k] int64, top_score [B,k], rank [B] int32) as ``rank_all``
+    (+ the dense scores [B,P] with ``return_scores``)."""
+    msg = model._rank_all_refusal()
+    if msg is not None:
+        raise NotImplementedError(msg)
+    if index.model is not model:
+        raise RuntimeError("rank_all_rtm: the catalogue index belongs to another model")
+    if index.stale():
+        raise RuntimeError("rank_all_rtm: stale catalogue index — a weight, a table or the catalogue changed since "
+                           "model.catalogue_index() built it; build it again")
+    lib = _lib.load()
+    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
+    ur = model._idx(batch.u_ridxs, 'u_ridxs')
+    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
+    B, Q = qw.shape
+    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,):
+        raise RuntimeError("rank_all_rtm: u_ridxs must be [B, U] and target_prod_idxs [B]")
+    ps, _ = model._structs()
+    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
+    k = int(topk)
+    dev = qw.device
+    nbytes = lib.ps_rtm_rank_scratch_bytes(desc, sh, k, int(items_per_pass or 0))
+    if nbytes < 0:
+        raise RuntimeError("rank_all_rtm: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
+    # exactly nbytes: the C entry sizes its passes from the scratch it is given, so the buffer is part of the result's shape
+    scratch = model.__dict__.get('_rtm_rank_scratch')
+    if scratch is None or scratch.numel() != nbytes or scratch.device != dev:
+        scratch = model.__dict__['_rtm_rank_scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    P = index.shape3[0]
+    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, P, dtype=torch.float32, device=dev) if return_scores else None
+    _lib.check(lib.ps_rtm_rank_all(desc, sh, ps, index.index.data_ptr(), index.item_ridxs.data_ptr(), qw.data_ptr(),
+                                   ur.data_ptr(), target.data_ptr(), k, top_idx.data_ptr(), top_score.data_ptr(),
+                                   rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(), scratch.numel(),
+                                   torch.cuda.current_stream(dev).cuda_stream), 'ps_rtm_rank_all')
+    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+
+
 def calc_metrics(rank, cutoff=100):
     """``Trainer.calc_metrics`` (trainer.py:172-187) from the 1-based ranks of ``rank_all``."""
     r = torch.as_tensor(rank).detach().cpu().numpy().astype(np.int64)

@@ -20,6 +20,11 @@ import torch
 from . import _lib
 
 
+# Steps taken by ANY Optimizer of this process.  A step reaches the parameters through raw pointers, which torch's version
+# counters do not see: whoever caches something derived from weights (ProductRanker.catalogue_index) reads this beside them.
+STEPS_TAKEN = [0]
+
+
 class Optimizer(object):
     METHODS = {'adam': 0, 'sgd': 1, 'adagrad': 2, 'adadelta': 3}                      # PsAdamHyper.method
     # state tensor names per parameter in torch.optim's state_dict() (first -> the plan's `m`, second -> its `v`)
@@ -208,6 +213,7 @@ class Optimizer(object):
         lib = _lib.load()
         plan = None if self._sharded is not None else (self._plan if self._plan_ok() else self._build_plan())
         self._step += 1
+        STEPS_TAKEN[0] += 1
         self._lazy_awaiting_step = False
         if self.decay_method == "noam":      # host mirror of the in-kernel schedule (optimizers.py:214-219)
             self.learning_rate = self.original_lr * min(self._step ** (-0.5),

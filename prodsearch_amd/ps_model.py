@@ -41,6 +41,16 @@ class _ReviewEncoder(_Holder):
             self.context_embeddings = word_embeddings
 
 
+class _CatalogueIndex(object):
+    """What ``ProductRanker.catalogue_index`` returns: the projection, the catalogue it serves and what it was built from."""
+    __slots__ = ('model', 'index', 'item_ridxs', 'review_u_p', 'shape3', 'stamp', 'table')
+
+    def stale(self):
+        """A weight, a table, the catalogue or the review-embedding table it was projected from has changed (the table it
+        was built from is held here, so clearing the model's copy does not by itself make the projection stale)."""
+        return self.model._rank_all_stamp(self.item_ridxs, self.review_u_p, self.table) != self.stamp
+
+
 class ProductRanker(HotPathModule):
     def __init__(self, args, device, vocab_size, review_count, product_size, user_size,
                  review_words, vocab_words, word_dists=None):
@@ -157,6 +167,92 @@ class ProductRanker(HotPathModule):
         _lib.check(lib.ps_rtm_review_embeddings(d, ps, self.review_words.data_ptr(), _lib.ptr(scratch), out.data_ptr(),
                                                 self._stream()), 'ps_rtm_review_embeddings')
         self.review_embeddings = out
+        self.__dict__['_rev_emb_stamp'] = self._rank_all_stamp()      # (catalogue_index: is this table still the weights'?)
+
+    # ------------------------------------------------------- the whole catalogue in one pass (evaluate.rank_all_rtm)
+    def _rank_all_refusal(self):
+        """Why ``catalogue_index`` / ``rank_all_rtm`` cannot serve this configuration (the message names the flag), or None.
+        ``PretrainedProductRanker`` is served: it inherits ``test``, which reads the same ``review_embeddings`` table."""
+        a = self.args
+        if a.inter_layers != 1:
+            return ("rank_all_rtm: inter_layers = %d — one encoder layer is built (deeper encoders need every position of "
+                    "layer 0)" % a.inter_layers)
+        if getattr(a, 'do_seq_review_test', False) and not a.train_review_only:
+            return ("rank_all_rtm: do_seq_review_test without train_review_only — an item's review list then depends on "
+                    "the entry")
+        if self.fix_emb and self.review_encoder_name in ('fs', 'avg'):
+            return "rank_all_rtm: fix_emb with the fs / avg review encoders is not built"
+        return None
+
+    def _rank_all_stamp(self, *extra):
+        """What something derived from the weights was built from: storage and torch version of every hot parameter
+        (``load_state_dict``, ``.to``, in-place edits) and of ``extra``, and the number of optimizer steps this process has
+        taken (``optimizers.STEPS_TAKEN``: the step kernels write the parameters through raw pointers, which the version
+        counters do not see; a step on another model counts too — a needless rebuild, never a stale result)."""
+        from .optimizers import STEPS_TAKEN
+        ts = [p for _, p in self._named_hot_params()] + [t for t in extra if t is not None]
+        return tuple((t.data_ptr(), t._version) for t in ts), STEPS_TAKEN[0]
+
+    def _rank_all_desc(self, B, Q, shape_U, index_shape=None):
+        a = self.args
+        d = self._desc(B, 0, int(a.uprev_review_limit) + int(a.iprev_review_limit), True, 1, Q)
+        sh = _lib.PsRtmRankShape()
+        if index_shape is not None:
+            sh.n_items, sh.review_u_p_rows, sh.I = index_shape
+        sh.U = shape_U
+        sh.seq_review_test = int(bool(getattr(a, 'do_seq_review_test', False)) and not a.train_review_only)
+        sh.fix_emb = int(self.fix_emb)
+        return d, sh
+
+    def catalogue_index(self, item_ridxs, review_u_p=None):
+        """The per-evaluation projection of ``evaluate.rank_all_rtm`` (``ps_rtm_rank_index``): every review's key / value
+        rows and the [segment][position] tables.  ``item_ridxs`` [P, I] int64 on the device: each product's reviews, then the
+        review pad id (``ProdSearchDataLoader.catalogue_reviews``).  ``review_u_p`` [n_reviews, 2] (author, item) is read only
+        with ``use_user_emb`` / ``use_item_emb``.  Builds ``review_embeddings`` if needed.  Cached: the same inputs and
+        unchanged weights give the same object back; an index whose sources changed is refused by ``rank_all_rtm``.  A cached
+        pvc / fs / avg review table that the weights have moved away from is rebuilt first."""
+        msg = self._rank_all_refusal()
+        if msg is not None:
+            raise NotImplementedError(msg)
+        lib = _lib.load()
+        item_ridxs = self._idx(item_ridxs, 'item_ridxs')
+        if item_ridxs.dim() != 2:
+            raise RuntimeError("item_ridxs must be [P, I]")
+        need_up = self.use_user_emb or self.use_item_emb
+        if need_up:
+            if review_u_p is None:
+                raise RuntimeError("use_user_emb / use_item_emb: catalogue_index needs review_u_p")
+            review_u_p = torch.as_tensor(np.asarray(review_u_p), dtype=torch.int64).reshape(-1, 2) \
+                if not torch.is_tensor(review_u_p) else review_u_p
+            review_u_p = self._idx(review_u_p.to(self._dev()), 'review_u_p')
+        else:
+            review_u_p = None
+        # the review table the projection reads: a pvc / fs / avg table computed from weights that have changed since (an
+        # optimizer step without clear_review_embbeddings()) is computed again; pv / fix_emb: the parameter itself
+        if self.review_embeddings is not None and self.review_encoder_name != 'pv' and \
+                self.__dict__.get('_rev_emb_stamp') != self._rank_all_stamp():
+            self.review_embeddings = None
+        if self.review_embeddings is None:
+            self.get_review_embeddings()
+        stamp = self._rank_all_stamp(item_ridxs, review_u_p, self.review_embeddings)
+        cached = self.__dict__.get('_cat_index')
+        if cached is not None and cached.stamp == stamp:
+            return cached
+        ps, _ = self._structs()
+        shape3 = (item_ridxs.shape[0], 0 if review_u_p is None else review_u_p.shape[0], item_ridxs.shape[1])
+        d, sh = self._rank_all_desc(1, 1, 1, shape3)
+        n = lib.ps_rtm_rank_index_floats(d, sh)
+        if n < 0:
+            raise RuntimeError("ps_rtm_rank_index_floats: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
+        out = torch.empty(n, device=self._dev(), dtype=torch.float32)
+        tab = self.review_embeddings.detach().contiguous()
+        _lib.check(lib.ps_rtm_rank_index(d, sh, ps, tab.data_ptr(), _lib.ptr(review_u_p), out.data_ptr(), self._stream()),
+                   'ps_rtm_rank_index')
+        idx = _CatalogueIndex()
+        idx.model, idx.index, idx.item_ridxs, idx.review_u_p, idx.shape3, idx.stamp = self, out, item_ridxs, review_u_p, shape3, stamp
+        idx.table = self.review_embeddings
+        self.__dict__['_cat_index'] = idx
+        return idx
 
     def forward(self, batch_data, train_pv=True, neg_word_idxs=None):
         return self._loss_forward(*self._run_forward(batch_data, bool(train_pv), neg_word_idxs))

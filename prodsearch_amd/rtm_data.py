@@ -73,6 +73,29 @@ class ProdSearchTestBatch(object):
                               mv(self.candi_seq_user_idxs), mv(self.candi_seq_item_idxs), to_tensor=False)
 
 
+class ProdSearchRankBatch(object):
+    """Entries-only evaluation batch of the full-catalogue pass (``evaluate.rank_all_rtm``): what an entry brings to every
+    candidate's sequence — its query words and its user's previous reviews — plus the target.  The items' side is one
+    ``[P, I]`` matrix for the whole evaluation (``ProdSearchDataLoader.catalogue_reviews``).
+
+        query_word_idxs   [B,Q]   pad V-1
+        u_ridxs           [B,U]   the user's reviews (``get_user_review_idxs``), then the pad review
+        target_prod_idxs  [B]     int64 tensor
+    """
+    def __init__(self, query_idxs, user_idxs, target_prod_idxs, query_word_idxs, u_ridxs):
+        self.query_idxs, self.user_idxs = query_idxs, user_idxs
+        self.target_prod_idxs = _t(target_prod_idxs)
+        self.query_word_idxs = _t(query_word_idxs)
+        self.u_ridxs = _t(u_ridxs)
+
+    def to(self, device):
+        if device == "cpu":
+            return self
+        mv = lambda x: x.to(device, non_blocking=True)
+        return self.__class__(self.query_idxs, self.user_idxs, mv(self.target_prod_idxs), mv(self.query_word_idxs),
+                              mv(self.u_ridxs))
+
+
 def make_review_words(seed, review_count, vocab_size, word_limit, word_dists=None):
     """[review_count, WL] padded review texts; the last review is the pad review (all pad words),
     as ``ProdSearchData.sub_sampling`` + ``pad`` build it (data/data_util.py:138-153)."""

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, pyrandom
 from .dataloader import _csr, prefetch_iter, sampler_batches
-from .rtm_data import ProdSearchTestBatch, ProdSearchTrainBatch
+from .rtm_data import ProdSearchRankBatch, ProdSearchTestBatch, ProdSearchTrainBatch
 
 _np_handle = None
 
@@ -267,6 +267,61 @@ class ProdSearchDataLoader(object):
         return ProdSearchTestBatch(quad[:, 0].tolist(), quad[:, 1].tolist(), quad[:, 2].tolist(), candi,
                                    self._ship(qw), self._ship(ridx[:B * Cw * Rc].view(B, Cw, Rc)), seg, usr, itm,
                                    to_tensor=False)
+
+    # ------------------------------------------------------------------ the whole catalogue in one pass (evaluate.rank_all_rtm)
+    def _rank_all_check(self):
+        if self._train:
+            raise RuntimeError("catalogue_reviews / rank batches belong to an evaluation loader")
+        if self.args.do_seq_review_test and not self.args.train_review_only:
+            raise NotImplementedError("rank_all_rtm: do_seq_review_test without train_review_only — an item's review list "
+                                      "then depends on the entry (prod_search_dataloader.py:63, 73-85)")
+        if int(self.args.uprev_review_limit) < 1 or int(self.args.iprev_review_limit) < 1:
+            raise NotImplementedError("rank_all_rtm: uprev_review_limit and iprev_review_limit must be at least 1")
+
+    def catalogue_reviews(self):
+        """``[P, iprev_review_limit]`` review ids of every product, padded with the review pad id: the rule of the test
+        collate without ``do_seq_review_test`` — ``get_item_review_idxs(candi_i, None, False, ..., fix=True)``, the last
+        ``iprev_review_limit`` TRAIN reviews of the item (prod_search_dataloader.py:78-85, 170-194) — which does not depend
+        on the entry."""
+        self._rank_all_check()
+        c, lim = self.corpus, int(self.args.iprev_review_limit)
+        out = np.full((c.n_products, lim), self.review_pad_idx, dtype=np.int64)
+        for p in range(c.n_products):
+            s = c.it_seq[c.it_seq_ptr[p]:c.it_seq_ptr[p + 1]][-lim:]
+            out[p, :len(s)] = s
+        return self._ship(torch.from_numpy(out))
+
+    def rank_entries(self):
+        """Positions in the dataset of its distinct (query, user, product, review) entries: the dataset repeats an entry once
+        per candidate chunk (prod_search_dataset.py:43-83), consecutively."""
+        q = self.entry_quad
+        keep = np.ones(len(q), dtype=bool)
+        keep[1:] = (q[1:] != q[:-1]).any(1)
+        return np.flatnonzero(keep)
+
+    def rank_batch_from_ids(self, ids):
+        """Entries-only batch: the user's review ids as ``get_user_review_idxs(user, review, False, ..., fix=True)`` gives them
+        (:64, 135-168: the user's TRAIN reviews other than the entry's, the last ``uprev_review_limit``), the query words and
+        the target."""
+        self._rank_all_check()
+        ids = np.asarray(ids, dtype=np.int64)
+        quad = self.entry_quad[ids]
+        c, lim = self.corpus, int(self.args.uprev_review_limit)
+        u_r = np.full((len(ids), lim), self.review_pad_idx, dtype=np.int64)
+        for b, (_, user, _, review) in enumerate(quad):
+            s = c.ut_seq[c.ut_seq_ptr[user]:c.ut_seq_ptr[user + 1]]
+            s = s[s != review][-lim:]
+            u_r[b, :len(s)] = s
+        qw = torch.from_numpy(np.ascontiguousarray(c.query_words[quad[:, 0]]))
+        return ProdSearchRankBatch(quad[:, 0].tolist(), quad[:, 1].tolist(),
+                                   self._ship(torch.from_numpy(np.ascontiguousarray(quad[:, 2]))), self._ship(qw),
+                                   self._ship(torch.from_numpy(u_r)))
+
+    def rank_batches(self):
+        """The dataset's distinct entries, ``batch_size`` at a time."""
+        ent = self.rank_entries()
+        for lo in range(0, len(ent), self.batch_size):
+            yield self.rank_batch_from_ids(ent[lo:lo + self.batch_size])
 
     # ------------------------------------------------------------------ the reference's collate_fn entry points
     def get_train_batch(self, batch):
