@@ -603,6 +603,20 @@ int ps_rtm_rank_index(const PsRtmDesc* desc, const PsRtmRankShape* shape, const 
 /* bytes of scratch for ps_rtm_rank_all with `items_per_pass` items scored per pass (<= 0: the default, 32768 pairs);
  * -1: refused / bad sizes.  ps_rtm_rank_all sizes its passes from the scratch it is given: the most items that fit. */
 int64_t ps_rtm_rank_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t items_per_pass);
+/* What ps_rtm_rank_all launches for this descriptor, shape, topk and scratch size, from the rules the launcher itself reads
+ * (csrc/rtm_rank.hip: rr_pass_layout, rr_epl, rr_lph, rr_items_per_workgroup, rr_pair_lds, rr_tail_fused, rr_query_fs_fused).  Host only: no
+ * HIP call, works without a device; reads the process's switches (PS_NO_FUSE).  Refused as ps_rtm_rank_all refuses. */
+typedef struct PsRtmRankPlan {
+  int64_t items_per_pass;       /* items scored per pass: the most whose pairs fit the scratch                         */
+  int64_t passes;               /* ceil(n_items / items_per_pass)                                                      */
+  int32_t epl;                  /* d / 64: columns per lane, the instantiation of rr_entry_kernel / rr_pair_kernel     */
+  int32_t lph;                  /* 64 / H: lanes per head, the width of the cross-lane sum of a logit                  */
+  int32_t items_per_workgroup;  /* items whose K / V rows one workgroup of rr_pair_kernel holds in LDS                 */
+  int32_t lds_bytes;            /* that tile's dynamic LDS; above 64 KB the launcher raises the kernel's limit first   */
+  int32_t tail_fused;           /* the per-pair tail is the fused d = 128 kernel (0: GEMMs and row kernels)            */
+  int32_t query_fs_fused;       /* the fs query encoder's projection runs inside the embed launch (0: a GEMM, or avg)  */
+} PsRtmRankPlan;
+int ps_rtm_rank_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t scratch_bytes, PsRtmRankPlan* out);
 /* item_ridxs [P, I]; query_word_idxs [B, Q]; u_ridxs [B, U]; target_prod_idxs [B] (NULL: no rank).  top_idx / top_score
  * [B, topk], rank [B]: the semantics of ps_rank_all (score desc, id asc; rank 1-based, 0: the target is not an item;
  * topk <= 256; unfilled slots -1 / -inf).  scores_out (optional) [B, P] dense.  scratch: 256-byte aligned. */

@@ -128,6 +128,11 @@ class PsRtmRankShape(C.Structure):
                [(n, C.c_int32) for n in ('I', 'U', 'seq_review_test', 'fix_emb')]
 
 
+class PsRtmRankPlan(C.Structure):
+    _fields_ = [('items_per_pass', C.c_int64), ('passes', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('epl', 'lph', 'items_per_workgroup', 'lds_bytes', 'tail_fused', 'query_fs_fused')]
+
+
 # every symbol include/prodsearch_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     'ps_version': (C.c_char_p, []),
@@ -173,6 +178,7 @@ SYMBOLS = {
     'ps_rtm_rank_index': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.POINTER(PsRtmTensors), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     'ps_rtm_rank_scratch_bytes': (C.c_int64, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int32, C.c_int64]),
+    'ps_rtm_rank_plan': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int32, C.c_int64, C.POINTER(PsRtmRankPlan)]),
     'ps_rtm_rank_all': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.POINTER(PsRtmTensors)] +
                         [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
     'ps_sample_negatives': (C.c_int, [C.POINTER(PsTemDesc), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -398,9 +398,54 @@ extern "C" int64_t ps_rtm_rank_scratch_bytes(const PsRtmDesc* desc, const PsRtmR
   return r.total * (int64_t)sizeof(float);
 }
 
+// ---- what a call launches: ps_rtm_rank_all and ps_rtm_rank_plan read the same rules
+// items per workgroup: as many as ~48 KB of K / V rows hold (at least one), so several workgroups share a CU
+static int rr_items_per_workgroup(int I, int d, int tile) {
+  const size_t per = (size_t)I * 2 * d * sizeof(float);
+  int it = (int)((48 * 1024) / per);
+  it = it < 1 ? 1 : (it > RR_IT_MAX ? RR_IT_MAX : it);
+  return it < tile ? it : tile;
+}
+static int rr_epl(const PsRtmDesc& D) { return D.d / 64; }     // columns per lane: the instantiation of the entry / pair kernels
+static int rr_lph(const PsRtmDesc& D) { return 64 / D.H; }     // lanes per head: the width of a logit's cross-lane sum
+static size_t rr_pair_lds(int IT, int I, int d) { return (size_t)IT * I * 2 * d * sizeof(float); }   // rr_pair_kernel's dynamic LDS
+static bool rr_query_fs_fused(const PsRtmDesc& D) { return D.query_encoder == PS_QENC_FS && ps_fusion_enabled() && D.d <= 128; }
+// the pass size comes from the scratch: the most items whose pairs fit (the layout grows with the tile)
+static int rr_pass_layout(const PsRtmDesc& D, const PsRtmRankShape& Sh, int topk, int64_t scratch_bytes, RrWs& r) {
+  TRY(rr_layout(D, Sh, topk, 1, r));
+  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_all: scratch %lld < %lld bytes (one item per pass)",
+             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
+  int64_t lo = 1, hi = Sh.n_items;
+  while ((int64_t)D.B * hi >= ((int64_t)1 << 30)) hi >>= 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    RrWs t;
+    if (rr_layout(D, Sh, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
+  }
+  return rr_layout(D, Sh, topk, lo, r);
+}
+
+extern "C" int ps_rtm_rank_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t scratch_bytes,
+                                PsRtmRankPlan* out) {
+  PS_REQUIRE(desc && shape && out, "rtm rank plan: null argument");
+  memset(out, 0, sizeof(*out));
+  TRY(rr_check(*desc, *shape));
+  RrWs r;
+  TRY(rr_pass_layout(*desc, *shape, topk, scratch_bytes, r));
+  out->items_per_pass = r.tile;
+  out->passes = (shape->n_items + r.tile - 1) / r.tile;
+  out->epl = rr_epl(*desc);
+  out->lph = rr_lph(*desc);
+  out->items_per_workgroup = rr_items_per_workgroup(shape->I, desc->d, r.tile);
+  out->lds_bytes = (int32_t)rr_pair_lds(out->items_per_workgroup, shape->I, desc->d);
+  out->tail_fused = r.fuse ? 1 : 0;
+  out->query_fs_fused = rr_query_fs_fused(*desc) ? 1 : 0;
+  return PS_OK;
+}
+
 template <int EPL>
 static int rr_launch_pair(const RrK& k, hipStream_t st) {
-  const size_t lds = (size_t)k.IT * k.I * 2 * k.d * sizeof(float);
+  const size_t lds = rr_pair_lds(k.IT, k.I, k.d);
   // (a function attribute is per device: set whenever the tile needs more than the default 64 KB, not once per process)
   if (lds > 64 * 1024)
     PS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rr_pair_kernel<EPL>), hipFuncAttributeMaxDynamicSharedMemorySize, RR_LDS_MAX));
@@ -430,21 +475,8 @@ extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shap
   PS_REQUIRE(!D.use_item_emb || P.product_emb, "rtm rank_all: use_item_emb needs product_emb");
   const int B = D.B, d = D.d;
   const int64_t NP = Sh.n_items;
-  // the pass size comes from the scratch: the most items whose pairs fit (the layout grows with the tile)
   RrWs r;
-  TRY(rr_layout(D, Sh, topk, 1, r));
-  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_all: scratch %lld < %lld bytes (one item per pass)",
-             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
-  {
-    int64_t lo = 1, hi = NP;
-    while ((int64_t)B * hi >= ((int64_t)1 << 30)) hi >>= 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) / 2;
-      RrWs t;
-      if (rr_layout(D, Sh, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
-    }
-    TRY(rr_layout(D, Sh, topk, lo, r));
-  }
+  TRY(rr_pass_layout(D, Sh, topk, scratch_bytes, r));
   hipStream_t st = (hipStream_t)stream;
   float* ws = reinterpret_cast<float*>(scratch);
   const RrIndex x = rr_index_layout(D);
@@ -461,7 +493,7 @@ extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shap
   e.drop_fs = make_drop(E, PS_SITE_FS);
   e.qmean_d = ws + r.qmean; e.query_emb = ws + r.qemb;
   PS_REQUIRE(!e.fs || (P.fs_w && P.fs_b), "rtm rank_all: null FS encoder weights");
-  const bool fs_fused = e.fs && ps_fusion_enabled() && d <= 128;
+  const bool fs_fused = rr_query_fs_fused(D);
   if (fs_fused) { e.fs_w = P.fs_w; e.fs_b = P.fs_b; }
   if (r.fuse) { e.split = make_wsplit(E, Tt, ws, r.w); e.split_fwd_only = 1; }
   PS_REQUIRE(!r.fuse || e.split.on, "rtm rank_all: the fused tail's weight split is missing");
@@ -488,21 +520,16 @@ extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shap
   }
   RrK k;
   memset(&k, 0, sizeof(k));
-  k.B = B; k.d = d; k.lph = 64 / D.H; k.I = Sh.I; k.U = Sh.U; k.T1 = x.T1; k.tile = r.tile; k.P = (int)NP; k.ldS = (int)r.ldS;
+  k.B = B; k.d = d; k.lph = rr_lph(D); k.I = Sh.I; k.U = Sh.U; k.T1 = x.T1; k.tile = r.tile; k.P = (int)NP; k.ldS = (int)r.ldS;
   k.RC = D.review_count;
   k.item_r = item_ridxs; k.u_r = u_ridxs;
   k.KR = index + x.KR; k.VR = index + x.VR; k.kt = index + x.kt; k.vt = index + x.vt;
   k.qp = ws + r.qp; k.k0 = ws + r.k0; k.v0 = ws + r.v0;
   k.em = ws + r.em; k.es = ws + r.es; k.eacc = ws + r.eacc; k.entn = reinterpret_cast<int32_t*>(ws + r.entn);
   k.ctx = ws + r.w.layer[0].ctx;
-  {   // items per workgroup: as many as ~48 KB of K / V rows hold (at least one), so several workgroups share a CU
-    const size_t per = (size_t)Sh.I * 2 * d * sizeof(float);
-    int it = (int)((48 * 1024) / per);
-    it = it < 1 ? 1 : (it > RR_IT_MAX ? RR_IT_MAX : it);
-    k.IT = it < r.tile ? it : r.tile;
-  }
+  k.IT = rr_items_per_workgroup(Sh.I, d, r.tile);
   const dim3 eg(ps_cdiv(B, 4));
-  const int epl = d / 64;
+  const int epl = rr_epl(D);
   if (epl == 1) hipLaunchKernelGGL(rr_entry_kernel<1>, eg, dim3(256), 0, st, k);
   else if (epl == 2) hipLaunchKernelGGL(rr_entry_kernel<2>, eg, dim3(256), 0, st, k);
   else if (epl == 4) hipLaunchKernelGGL(rr_entry_kernel<4>, eg, dim3(256), 0, st, k);

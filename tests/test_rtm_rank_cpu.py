@@ -77,33 +77,89 @@ def test_loader_refuses_entry_dependent_item_lists(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------- 2. the factorisation
-CASES = {'base': dict(),
-         'pv_user_item': dict(encoder='pv', use_user_emb=True, use_item_emb=True),
-         'no_pos': dict(use_pos_emb=False),
-         'no_seg': dict(use_seg_emb=False),
-         'long': dict(U=20, I=30, P=70, B=3, RC=2500)}
+CASES = U.CASES          # every case the GPU file runs (tests/rtm_rank_util.py), computed once per name (U.host_case)
+
+
+def test_case_tables_cover_the_same_names():
+    assert set(U.CASES) == set(U.PLAN) == set(U.YARDSTICK)
+    assert all(set(p) <= set(U.PLAN_FIELDS) for p in U.PLAN.values())
+    assert all(0 < U.bound(n) <= U.TOL for n in U.CASES)
 
 
 @pytest.mark.parametrize('name', sorted(CASES))
 def test_factorisation_is_exact_in_float64(name):
     """The split softmax + linear key / value decomposition against ``rtm_test``: 1e-10 in float64; in fp32 the figure is what
     the re-association alone costs — the yardstick beside the GPU's 1e-4 bound (profiles/rtm_rank_all.md: it stays two orders
-    below it).  Also: at synth.make_state_dict's scale at most a quarter of the oracle's order lies in a 2 * tol band."""
-    c = U.make_case(**CASES[name])
-    _, sd = U.build_model(c, 'cpu')
-    T = c.U + c.I
-    ref64, P64, rev64 = U.oracle_scores(c, sd, f64=True)
-    got64 = U.factorised_scores(P64, c.a, c.qw, c.u_r, c.item_r, rev64, c.review_u_p, c.V, c.RC, T)
-    e64 = rel_err(got64, ref64)
-    ref32, P32, rev32 = U.oracle_scores(c, sd, f64=False)
-    got32 = U.factorised_scores(P32, c.a, c.qw, c.u_r, c.item_r, rev32, c.review_u_p, c.V, c.RC, T)
-    e32, o32 = rel_err(got32, ref64), rel_err(ref32, ref64)
-    _, band = U.banded(ref32)
+    below it).  Also: at synth.make_state_dict's scale at most a quarter of the oracle's order lies in a 2 * tol band.
+    The two sides cut a sequence independently (``assemble_chunk(limit=)`` feeds the oracle, ``factorised_scores`` cuts by the
+    kernel's counts), so the ``cap`` cases pin the rule itself."""
+    h = U.host_case(name)
+    e64 = rel_err(h.f64, h.ref64)
+    e32, o32 = rel_err(h.f32, h.ref64), rel_err(h.ref32, h.ref64)
+    _, band = U.banded(h.ref32)
     print('%s: factorised f64 %.3g, factorised fp32 vs f64 %.3g, rtm_test fp32 vs f64 %.3g, banded %.3f'
           % (name, e64, e32, o32, band.mean()))
     assert e64 < 1e-10
+    assert U.entry_err(h.f64, h.ref64).max() < 1e-10
     assert e32 < U.TOL
     assert band.mean() <= 0.25
+
+
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_recorded_yardstick_still_holds(name):
+    """``U.YARDSTICK[name]``: the worst entry's error of fp32 on the host (the fp32 oracle, the fp32 factorisation) against the
+    float64 oracle, re-measured; a tenth on top for this host's summation order.  The GPU's per-entry bound is 8 x the record."""
+    h = U.host_case(name)
+    print('%s: yardstick measured %.3g, recorded %.3g, bound %.3g' % (name, h.yard, U.YARDSTICK[name], U.bound(name)))
+    assert h.yard <= 1.1 * U.YARDSTICK[name]
+
+
+def test_the_cases_hold_what_they_were_written_for():
+    pad = lambda c: c.RC - 1
+    c = U.host_case('lds_full').c                                          # a full ballot on both sides: 64 live ids
+    assert U.leading(c.u_r.numpy(), pad(c))[1] == 64 and U.leading(c.item_r.numpy(), pad(c))[1] == 64
+    c = U.host_case('cap').c                                               # T = 5 review positions under lists of 4 and 6
+    nu, ni = U.leading(c.u_r.numpy(), pad(c)), U.leading(c.item_r.numpy(), pad(c))
+    assert c.T == 5 and nu[1] == 4 and ((nu >= 2) & (nu <= 4)).sum() >= 2  # the full user list leaves every item one review
+    assert (ni[None, :] > c.T - nu[:, None]).any(1).all()                   # every entry has items that are cut
+    c = U.host_case('cap_user').c
+    nu, ni = U.leading(c.u_r.numpy(), pad(c)), U.leading(c.item_r.numpy(), pad(c))
+    assert c.T == 5 and nu[1] == 6                                          # cut to 5: the user's list alone fills the sequence
+    assert ((nu >= 2) & (nu < 5)).any() and (ni > 3).any()
+    h = U.host_case('cap_user')
+    assert (h.keys[1] == 6).all()                                           # n = 0 for every item: one score for the whole catalogue
+    assert float((h.ref64[1] - h.ref64[1, 0]).abs().max()) < 1e-12 * float(h.ref64[1].abs().max())
+    # sharp: on the float64 side some pair's softmax over at least four keys puts more than 0.99 on one of them; base does not
+    hs, hb = U.host_case('sharp'), U.host_case('base')
+    assert float(hs.wmax[hs.keys >= 4].max()) > 0.99 and float(hb.wmax[hb.keys >= 4].max()) < 0.9
+
+
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_one_mistake_in_the_kernel_would_exceed_the_bound(name):
+    """What the per-entry bound (8 x yardstick) still catches, in float64: ``factorised_scores(fault=...)`` makes one mistake
+    of the kind the kernels could make, and every entry it acts on must move its error by at least twice the bound; where a
+    mistake cannot act by construction (no positions / no segments / nothing to cut / one head) the scores are the same bits."""
+    h = U.host_case(name)
+    base = U.entry_err(h.f64, h.ref64)
+    a = h.c.a
+    for fault in U.FAULTS:
+        s, acts = U.faulty_scores(h, fault)
+        moved = np.abs(U.entry_err(s, h.ref64) - base)
+        print('%s %-12s acts on %d of %d entries, moves them by %.3g .. %.3g (bound %.3g)'
+              % (name, fault, acts.sum(), len(acts), moved[acts].min() if acts.any() else 0, moved[acts].max() if acts.any() else 0,
+                 U.bound(name)))
+        assert (moved[acts] >= 2 * U.bound(name)).all(), (name, fault, moved)
+        assert torch.equal(s[~acts], h.f64[~acts]), (name, fault)
+        expect_none = (fault == 'pos_off' and not a.use_pos_emb) or (fault == 'seg1_keys' and not a.use_seg_emb) or \
+                      (fault == 'no_cap' and not name.startswith('cap')) or (fault == 'heads_merged' and a.heads == 1)
+        assert acts.any() != expect_none, (name, fault)
+        if fault in ('no_cap', 'heads_merged') and not expect_none:
+            assert acts.all(), (name, fault)
+    if name == 'base':                                                      # orientation: the full item (6 reviews), its last key dropped
+        s, _ = U.faulty_scores(h, 'drop_last')
+        pair = ((s[:, 1] - h.ref64[:, 1]).abs() / h.ref64.abs().amax(1)).numpy()
+        print('base: item 1 without its last key moves its pairs by %.3g .. %.3g' % (pair.min(), pair.max()))
+        assert (pair >= 2 * U.bound(name)).all()
 
 
 # ------------------------------------------------------------------------------------------------- 3. ABI and refusals
@@ -113,7 +169,7 @@ def lib():
     return _lib.load()
 
 
-NEW = ('ps_rtm_rank_index_floats', 'ps_rtm_rank_index', 'ps_rtm_rank_scratch_bytes', 'ps_rtm_rank_all')
+NEW = ('ps_rtm_rank_index_floats', 'ps_rtm_rank_index', 'ps_rtm_rank_scratch_bytes', 'ps_rtm_rank_all', 'ps_rtm_rank_plan')
 
 
 def test_rank_all_symbols_declared_and_exported(lib):
@@ -123,6 +179,41 @@ def test_rank_all_symbols_declared_and_exported(lib):
     for name in NEW:
         assert name in _lib.SYMBOLS and hasattr(lib, name), name
     assert C.sizeof(_lib.PsRtmRankShape) == 32
+    assert C.sizeof(_lib.PsRtmRankPlan) == 40
+    body = re.search(r'typedef struct PsRtmRankPlan \{(.*?)\} PsRtmRankPlan;', hdr, re.S).group(1)
+    assert tuple(re.findall(r'int(?:32|64)_t\s+(\w+);', body)) == tuple(n for n, _ in _lib.PsRtmRankPlan._fields_)
+
+
+@pytest.mark.parametrize('name', sorted(U.CASES))
+def test_plan_of_every_case(lib, name):
+    """``ps_rtm_rank_plan`` (host only) for the call the GPU case makes: the branch each case was written for (``U.PLAN``), and
+    the fields that follow from the shape alone."""
+    h = U.host_case(name)
+    c = h.c
+    plan = U.plan_of(lib, h.m, c, 10, h.ipp)
+    print(name, plan)
+    for f, v in U.PLAN[name].items():
+        assert plan[f] == v, (name, f, plan[f], v)
+    assert plan['epl'] * 64 == c.a.embedding_size and plan['lph'] * c.a.heads == 64
+    assert plan['lds_bytes'] == plan['items_per_workgroup'] * c.I * 2 * c.a.embedding_size * 4 <= 128 * 1024
+    assert plan['passes'] == -(-c.P // plan['items_per_pass']) and plan['items_per_pass'] == (h.ipp or c.P)
+
+
+def test_plan_follows_the_scratch_and_refuses_as_the_launcher_does(lib):
+    c = U.make_case()
+    m, d, sh = _desc_shape(c)
+    plan = _lib.PsRtmRankPlan()
+    sizes = {n: lib.ps_rtm_rank_scratch_bytes(d, sh, 10, n) for n in (1, 8, 0)}
+    for n, want in ((1, 1), (8, 8), (0, c.P)):
+        assert lib.ps_rtm_rank_plan(d, sh, 10, sizes[n], plan) == 0
+        assert (plan.items_per_pass, plan.passes) == (want, -(-c.P // want))
+        assert plan.items_per_workgroup == min(8, want)                     # never more items than the pass holds
+    assert lib.ps_rtm_rank_plan(d, sh, 10, sizes[8] - 1, plan) == 0 and plan.items_per_pass == 7   # the most that fit
+    assert lib.ps_rtm_rank_plan(d, sh, 10, sizes[1] - 1, plan) != 0 and 'scratch' in lib.ps_last_error().decode()
+    assert lib.ps_rtm_rank_plan(d, sh, 257, sizes[0], plan) != 0
+    _, d2, sh2 = _desc_shape(c, n_layers=2)
+    assert lib.ps_rtm_rank_plan(d2, sh2, 10, sizes[0], plan) != 0 and 'inter_layers' in lib.ps_last_error().decode()
+    assert lib.ps_rtm_rank_plan(d, sh, 10, sizes[0], None) != 0
 
 
 def _desc_shape(c, **edit):
