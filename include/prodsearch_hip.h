@@ -624,6 +624,8 @@ int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shape, const Ps
                     const int64_t* item_ridxs, const int64_t* query_word_idxs, const int64_t* u_ridxs,
                     const int64_t* target_prod_idxs, int32_t topk, int64_t* top_idx, float* top_score, int32_t* rank,
                     float* scores_out, void* scratch, int64_t scratch_bytes, ps_stream_t stream);
+/* The same pass over per-entry candidate lists (sampled validation, the rerank of --test_candi_size lists): the entries of
+ * include/prodsearch_rtm_cand.h, which take this section's descriptor, shape and index. */
 
 /* Host evaluation of the dropout stream (tests pin oracle/philox.py to it): multiplier
  * (0 or 1/(1-p)) of element (row, col) of dropout site `site` at desc->seed/step/dropout. */

@@ -133,6 +133,11 @@ class PsRtmRankPlan(C.Structure):
                [(n, C.c_int32) for n in ('epl', 'lph', 'items_per_workgroup', 'lds_bytes', 'tail_fused', 'query_fs_fused')]
 
 
+class PsRtmRankCandPlan(C.Structure):
+    _fields_ = [('cands_per_pass', C.c_int64), ('passes', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('epl', 'lph', 'tail_fused', 'query_fs_fused')]
+
+
 # every symbol include/prodsearch_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     'ps_version': (C.c_char_p, []),
@@ -271,6 +276,15 @@ class PsRtmCollateArgs(C.Structure):
                 ('neg_per_pos', C.c_int32), ('user_pad', C.c_int64), ('prod_pad', C.c_int64), ('review_pad', C.c_int64)]
 
 
+# include/prodsearch_rtm_cand.h (the HIP library as well)
+RANK_CAND_SYMBOLS = {
+    'ps_rtm_rank_cand_scratch_bytes': (C.c_int64, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int64, C.c_int32, C.c_int64]),
+    'ps_rtm_rank_cand_plan': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int64, C.c_int32, C.c_int64,
+                                        C.POINTER(PsRtmRankCandPlan)]),
+    'ps_rtm_rank_candidates': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.POINTER(PsRtmTensors)] +
+                               [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+}
+
 # include/prodsearch_data.h (host-only library)
 DATA_SYMBOLS = {
     'ps_rtm_collate_train': (C.c_int, [C.POINTER(PsRtmCorpusView), C.POINTER(PsRtmCollateArgs), C.c_void_p, C.c_void_p,
@@ -346,7 +360,7 @@ def load():
         raise RuntimeError("libprodsearch_hip.so not found at %s: run `python -m prodsearch_amd.build` "
                            "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(RANK_CAND_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library drift
         fn.restype = res
         fn.argtypes = args

@@ -16,8 +16,14 @@
 //   rr_x0 / rr_entry       per entry: the query token's row, then the softmax state over its 1 + n_u keys (one wave per entry)
 //   rr_pair                per (entry, item): an item tile's K / V rows sit in LDS while the workgroup's waves walk the entries
 //   rr_head                wo . enc + b into the dense score matrix; the selection is rank.hip's (rank.h)
+// The same pass over per-entry CANDIDATE LISTS (include/prodsearch_rtm_cand.h, ps_rtm_rank_cand_* /
+// ps_rtm_rank_candidates: sampled validation, the rerank of test_candi_size lists) shares the index and the entry side:
+//   rr_cand                per (entry, slot of its list): one wave per pair, the K / V rows straight from KR / VR — no LDS tile,
+//                          two entries' lists have no item in common; the same rr_step in the same order as rr_pair
+//   rr_cand_head / _target / _ids   scores [B, C] (-inf at dead slots), the target's column, the selected columns -> item ids
 // fp32 throughout, plain C++; the per-pair tail is the encoder's own (enc_tail_forward).
 #include "rtm.h"
+#include "../../include/prodsearch_rtm_cand.h"
 #include "rank.h"
 #include "wgrad.h"      // gp / run1
 #include <math.h>
@@ -67,19 +73,20 @@ static RrIndex rr_index_layout(const PsRtmDesc& D) {
 struct RrWs {
   Ws w;                       // the tail's slice, laid out for enc_tail_forward: n_in = B, fan = tile, S = 1, qpos = 0
   int64_t qmean, qemb, x0, qp, k0, v0, em, es, eacc, entn, S, sel, total;
+  int64_t tcol;               // candidate lists only: the target's column per entry (int64)
   int64_t ldS, sel_bytes;
   int tile;
   bool fuse;
 };
 static bool rr_tail_fused(const PsRtmDesc& D) { return ps_fusion_enabled() && mlp_fused_serves(D.d, D.F); }
-static int rr_layout(const PsRtmDesc& D, const PsRtmRankShape& Sh, int topk, int64_t tile, RrWs& r) {
+// `cols` scored columns per entry (the catalogue's items, or the slots of a candidate list), `tile` of them per pass
+static int rr_layout_cols(const PsRtmDesc& D, int64_t cols, int topk, int64_t tile, const char* what, RrWs& r) {
   memset(&r, 0, sizeof(r));
-  const int64_t B = D.B, d = D.d, F = D.F, P = Sh.n_items;
-  PS_REQUIRE(tile >= 1 && tile <= P && B * tile < ((int64_t)1 << 30), "rtm rank_all: %lld items per pass", (long long)tile);
+  const int64_t B = D.B, d = D.d, F = D.F, P = cols;
   r.tile = (int)tile;
   r.fuse = rr_tail_fused(D);
   r.sel_bytes = rank_select_scratch_bytes((int)B, P, topk);
-  PS_REQUIRE(r.sel_bytes >= 0, "rtm rank_all: topk must be 1..256");
+  PS_REQUIRE(r.sel_bytes >= 0, "%s: topk must be 1..256", what);
   int64_t cur = 0;
   r.qmean = rtake(cur, B * d); r.qemb = rtake(cur, B * d); r.x0 = rtake(cur, B * d);
   r.qp = rtake(cur, B * d); r.k0 = rtake(cur, B * d); r.v0 = rtake(cur, B * d);
@@ -101,6 +108,21 @@ static int rr_layout(const PsRtmDesc& D, const PsRtmRankShape& Sh, int topk, int
   r.total = cur;
   return PS_OK;
 }
+static int rr_layout(const PsRtmDesc& D, const PsRtmRankShape& Sh, int topk, int64_t tile, RrWs& r) {
+  const int64_t P = Sh.n_items;
+  PS_REQUIRE(tile >= 1 && tile <= P && (int64_t)D.B * tile < ((int64_t)1 << 30), "rtm rank_all: %lld items per pass", (long long)tile);
+  return rr_layout_cols(D, P, topk, tile, "rtm rank_all", r);
+}
+// a candidate list of C slots per entry, `tile` columns of it per pass: the same slices, plus the target's column
+static int rr_cand_layout(const PsRtmDesc& D, int64_t C, int topk, int64_t tile, RrWs& r) {
+  PS_REQUIRE(C >= 1 && C < ((int64_t)1 << 31), "rtm rank_candidates: %lld candidates per entry (at least 1)", (long long)C);
+  PS_REQUIRE(tile >= 1 && tile <= C && (int64_t)D.B * tile < ((int64_t)1 << 30), "rtm rank_candidates: %lld candidates per pass", (long long)tile);
+  TRY(rr_layout_cols(D, C, topk, tile, "rtm rank_candidates", r));
+  int64_t cur = r.total;
+  r.tcol = rtake(cur, 2 * (int64_t)D.B);
+  r.total = cur;
+  return PS_OK;
+}
 
 // ------------------------------------------------------------------ kernels
 struct RrK {
@@ -111,6 +133,7 @@ struct RrK {
   const float *qp, *k0, *v0;
   float *em, *es, *eacc; int32_t* entn;
   float* ctx;
+  const int64_t* candi; int C;         // rr_cand_kernel: the lists [B, C]; i0 is then the pass's first column
 };
 
 // T[r] = rev[r] (+ user_emb[author]) (+ product_emb[item]) with the id rule of rtm_embed_kernel: an id outside [0, pad] adds nothing
@@ -304,6 +327,92 @@ __global__ __launch_bounds__(256) void rr_pair_kernel(const RrK a) {
   }
 }
 
+// per (entry, slot of the entry's own candidate list): one wave per pair.  Two entries' lists have no item in common, so an LDS
+// tile would amortise nothing: the K / V rows come by review id straight from KR / VR, as in rr_entry_kernel, the 2 * RR_U row
+// loads of a group issued together.  Slot t of the pass is column min(i0 + t, C - 1) (a ragged last pass runs at the full pass
+// shape); a dead slot (id outside [0, P)) is computed on item 0 — every load stays unconditional — and rr_cand_head_kernel writes
+// its score as -inf.  The walk is rr_pair_kernel's: the same rr_step on the same operands in the same groups, hence the same bits.
+template <int EPL>
+__global__ __launch_bounds__(256) void rr_cand_kernel(const RrK a) {
+  const int lane = threadIdx.x & 63;
+  const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  if (p >= a.B * a.tile) return;                    // (wave-uniform)
+  const int e = p / a.tile, t = p - e * a.tile;
+  const int d = a.d, pad = (int)(a.RC - 1);
+  int c = a.i0 + t;
+  c = c < a.C ? c : a.C - 1;
+  int64_t gi = a.candi[(size_t)e * a.C + c];
+  gi = (gi < 0 || gi >= a.P) ? 0 : gi;
+  const int id = lane < a.I ? (int)rclamp(a.item_r[(size_t)gi * a.I + lane], a.RC - 1) : pad;
+  const int nu = a.entn[e];
+  int n = rr_leading(id, pad);
+  n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;        // the sequence never exceeds 1 + total_review_limit positions
+  const size_t col = (size_t)lane * EPL;
+  const float* kt2 = a.kt + (size_t)a.T1 * d;
+  const float* vt2 = a.vt + (size_t)a.T1 * d;
+  float q[EPL], k[RR_U][EPL], v[RR_U][EPL], acc[EPL];
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) { q[i] = a.qp[(size_t)e * d + col + i]; acc[i] = a.eacc[(size_t)e * d + col + i]; }
+  float m = a.em[(size_t)e * 64 + lane], s = a.es[(size_t)e * 64 + lane];
+  for (int j = 0; j < n; j += RR_U) {
+#pragma unroll
+    for (int u = 0; u < RR_U; ++u) {
+      const int jj = j + u < n ? j + u : n - 1;     // (a slot past the list repeats its last row; rr_step drops it)
+      const size_t r = (size_t)__shfl(id, jj, 64);
+      const size_t pos = (size_t)(1 + nu + jj) * d + col;
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) {
+        k[u][i] = a.KR[r * d + col + i] + kt2[pos + i];
+        v[u][i] = a.VR[r * d + col + i] + vt2[pos + i];
+      }
+    }
+    rr_step<EPL>(q, k, v, n - j, a.lph, m, s, acc);
+  }
+  const float inv = 1.f / s;
+  float* out = a.ctx + ((size_t)e * a.tile + t) * d + col;
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) out[i] = acc[i] * inv;
+}
+
+// S[e][c0 + t] = wo . enc[e * tile + t] + b as rr_head_kernel, -inf for a dead slot
+__global__ __launch_bounds__(256) void rr_cand_head_kernel(const float* enc, const float* wo_w, const float* wo_b, const int64_t* candi,
+                                                           int B, int tile, int nv, int d, int c0, int C, int P, int ldS, float* S) {
+  const int lane = threadIdx.x & 63;
+  const int n = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  if (n >= B * tile) return;
+  const int e = n / tile, t = n - e * tile;
+  if (t >= nv) return;
+  float s = 0.f;
+  for (int c = lane; c < d; c += 64) s += enc[(size_t)n * d + c] * wo_w[c];
+  s = wave_sum(s) + wo_b[0];
+  const int64_t gi = candi[(size_t)e * C + c0 + t];
+  if (lane == 0) S[(size_t)e * ldS + c0 + t] = (gi < 0 || gi >= P) ? -INFINITY : s;
+}
+// the first live column of every entry's list that holds its target; C (not a column: rank 0) where there is none.  One wave per entry.
+__global__ __launch_bounds__(256) void rr_cand_target_kernel(const int64_t* candi, const int64_t* target, int B, int C, int P, int64_t* tcol) {
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  if (e >= B) return;
+  const int64_t tg = target[e];
+  const bool ok = tg >= 0 && tg < P;
+  int best = C;
+  for (int c0 = 0; c0 < C; c0 += 64) {
+    const int c = c0 + lane, cc = c < C ? c : C - 1;
+    const int64_t gi = candi[(size_t)e * C + cc];
+    best = (ok && c < best && gi == tg) ? c : best;   // (c < best <= C: a lane keeps its first hit)
+  }
+  for (int o = 32; o > 0; o >>= 1) { const int other = __shfl_xor(best, o, 64); best = other < best ? other : best; }
+  if (lane == 0) tcol[e] = best;
+}
+// the selected columns -> item ids; a dead slot that filled a place (fewer live slots than topk) reads as unfilled
+__global__ __launch_bounds__(256) void rr_cand_ids_kernel(const int64_t* candi, int B, int C, int topk, int64_t* top_idx, const float* top_score) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= B * topk) return;
+  const int e = n / topk;
+  const int64_t c = top_idx[n];
+  top_idx[n] = (c < 0 || c >= C || top_score[n] == -INFINITY) ? -1 : candi[(size_t)e * C + c];
+}
+
 // scores[e][i0 + t] = wo . enc[e * tile + t] + b  (rtm_score_kernel's sum order), one wave per pair
 __global__ __launch_bounds__(256) void rr_head_kernel(const float* enc, const float* wo_w, const float* wo_b, int B, int tile, int nv, int d,
                                                       int i0, int ldS, float* S) {
@@ -455,37 +564,26 @@ static int rr_launch_pair(const RrK& k, hipStream_t st) {
   return PS_OK;
 }
 
-extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
-                               const int64_t* item_ridxs, const int64_t* query_word_idxs, const int64_t* u_ridxs,
-                               const int64_t* target_prod_idxs, int32_t topk, int64_t* top_idx, float* top_score, int32_t* rank,
-                               float* scores_out, void* scratch, int64_t scratch_bytes, ps_stream_t stream) {
-  PS_REQUIRE(desc && shape && params && index && item_ridxs && query_word_idxs && u_ridxs && top_idx && top_score && scratch,
-             "rtm rank_all: null argument");
-  const PsRtmDesc& D = *desc;
-  const PsRtmRankShape& Sh = *shape;
-  const PsRtmTensors& P = *params;
-  TRY(rr_check(D, Sh));
-  TRY(rr_layer_check(P));
-  PS_REQUIRE(P.word_emb, "rtm rank_all: null word table");
-  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_all: rank needs target_prod_idxs");
-  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_all: scratch must be 256-byte aligned");
-  PS_REQUIRE(!D.use_seg_emb || P.seg_emb, "rtm rank_all: null segment table");
-  PS_REQUIRE(!D.use_pos_emb || P.pe, "rtm rank_all: null positional table");
-  PS_REQUIRE(!D.use_user_emb || P.user_emb, "rtm rank_all: use_user_emb needs user_emb");
-  PS_REQUIRE(!D.use_item_emb || P.product_emb, "rtm rank_all: use_item_emb needs product_emb");
+// ---- the entry side, once per call, for ps_rtm_rank_all and ps_rtm_rank_candidates alike: the shared query encoder (as
+// rtm_encode), the query token, K / V / Q of it, the softmax state over {query, the user's reviews}.  Fills the encoder's view of
+// the tensors and the kernels' arguments for the passes that follow.
+struct RrCall {
+  PsTemDesc E;
+  PsTemTensors Tt;                                   // the tail's view: no K / V streams in the weight split
+  RrK k;
+  int epl;
+};
+static int rr_entry_side(const PsRtmDesc& D, const PsRtmRankShape& Sh, const PsRtmTensors& P, const float* index, const int64_t* item_ridxs,
+                         const int64_t* query_word_idxs, const int64_t* u_ridxs, const RrWs& r, float* ws, hipStream_t st, RrCall& c) {
   const int B = D.B, d = D.d;
-  const int64_t NP = Sh.n_items;
-  RrWs r;
-  TRY(rr_pass_layout(D, Sh, topk, scratch_bytes, r));
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = reinterpret_cast<float*>(scratch);
   const RrIndex x = rr_index_layout(D);
-  const PsTemDesc E = rr_enc_desc(D);
+  c.E = rr_enc_desc(D);
+  const PsTemDesc& E = c.E;
   PsTemTensors T;
   rr_tem_tensors(P, T);
-  PsTemTensors Tt = T;                               // the tail's view: no K / V streams in the weight split
+  c.Tt = T;
+  PsTemTensors& Tt = c.Tt;
   Tt.layer[0].wk = nullptr; Tt.layer[0].wv = nullptr;
-  // ---- entry side, once per batch: the shared query encoder (as rtm_encode), the query token, K / V / Q of it, the softmax state
   EmbedArgs e;
   memset(&e, 0, sizeof(e));
   e.B = B; e.Q = D.Q; e.L = 0; e.S = 1; e.d = d; e.P = 1; e.V = D.vocab_size; e.tem = 0;
@@ -518,9 +616,9 @@ extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shap
     g.p[2].alpha = 1.f / sqrtf((float)(d / D.H));    // Q pre-divided by sqrt(dh) (neural.py:206)
     TRY(ps_launch_gemm(g, st));
   }
-  RrK k;
+  RrK& k = c.k;
   memset(&k, 0, sizeof(k));
-  k.B = B; k.d = d; k.lph = rr_lph(D); k.I = Sh.I; k.U = Sh.U; k.T1 = x.T1; k.tile = r.tile; k.P = (int)NP; k.ldS = (int)r.ldS;
+  k.B = B; k.d = d; k.lph = rr_lph(D); k.I = Sh.I; k.U = Sh.U; k.T1 = x.T1; k.tile = r.tile; k.P = (int)Sh.n_items; k.ldS = (int)r.ldS;
   k.RC = D.review_count;
   k.item_r = item_ridxs; k.u_r = u_ridxs;
   k.KR = index + x.KR; k.VR = index + x.VR; k.kt = index + x.kt; k.vt = index + x.vt;
@@ -529,23 +627,57 @@ extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shap
   k.ctx = ws + r.w.layer[0].ctx;
   k.IT = rr_items_per_workgroup(Sh.I, d, r.tile);
   const dim3 eg(ps_cdiv(B, 4));
-  const int epl = rr_epl(D);
-  if (epl == 1) hipLaunchKernelGGL(rr_entry_kernel<1>, eg, dim3(256), 0, st, k);
-  else if (epl == 2) hipLaunchKernelGGL(rr_entry_kernel<2>, eg, dim3(256), 0, st, k);
-  else if (epl == 4) hipLaunchKernelGGL(rr_entry_kernel<4>, eg, dim3(256), 0, st, k);
+  c.epl = rr_epl(D);
+  if (c.epl == 1) hipLaunchKernelGGL(rr_entry_kernel<1>, eg, dim3(256), 0, st, k);
+  else if (c.epl == 2) hipLaunchKernelGGL(rr_entry_kernel<2>, eg, dim3(256), 0, st, k);
+  else if (c.epl == 4) hipLaunchKernelGGL(rr_entry_kernel<4>, eg, dim3(256), 0, st, k);
   else hipLaunchKernelGGL(rr_entry_kernel<8>, eg, dim3(256), 0, st, k);
   PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+static int rr_tensor_check(const PsRtmDesc& D, const PsRtmTensors& P) {
+  TRY(rr_layer_check(P));
+  PS_REQUIRE(P.word_emb, "rtm rank_all: null word table");
+  PS_REQUIRE(!D.use_seg_emb || P.seg_emb, "rtm rank_all: null segment table");
+  PS_REQUIRE(!D.use_pos_emb || P.pe, "rtm rank_all: null positional table");
+  PS_REQUIRE(!D.use_user_emb || P.user_emb, "rtm rank_all: use_user_emb needs user_emb");
+  PS_REQUIRE(!D.use_item_emb || P.product_emb, "rtm rank_all: use_item_emb needs product_emb");
+  return PS_OK;
+}
+
+extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
+                               const int64_t* item_ridxs, const int64_t* query_word_idxs, const int64_t* u_ridxs,
+                               const int64_t* target_prod_idxs, int32_t topk, int64_t* top_idx, float* top_score, int32_t* rank,
+                               float* scores_out, void* scratch, int64_t scratch_bytes, ps_stream_t stream) {
+  PS_REQUIRE(desc && shape && params && index && item_ridxs && query_word_idxs && u_ridxs && top_idx && top_score && scratch,
+             "rtm rank_all: null argument");
+  const PsRtmDesc& D = *desc;
+  const PsRtmRankShape& Sh = *shape;
+  const PsRtmTensors& P = *params;
+  TRY(rr_check(D, Sh));
+  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_all: rank needs target_prod_idxs");
+  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_all: scratch must be 256-byte aligned");
+  TRY(rr_tensor_check(D, P));
+  const int B = D.B, d = D.d;
+  const int64_t NP = Sh.n_items;
+  RrWs r;
+  TRY(rr_pass_layout(D, Sh, topk, scratch_bytes, r));
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = reinterpret_cast<float*>(scratch);
+  RrCall c;
+  TRY(rr_entry_side(D, Sh, P, index, item_ridxs, query_word_idxs, u_ridxs, r, ws, st, c));
+  RrK& k = c.k;
   // ---- passes over item tiles: pair kernel -> the encoder's per-replica tail (n_in = B, fan = tile) -> head
   float* S = ws + r.S;
   for (int64_t i0 = 0; i0 < NP; i0 += r.tile) {
     k.i0 = (int)i0;
     k.nv = (int)(i0 + r.tile <= NP ? r.tile : NP - i0);
-    if (epl == 1) TRY(rr_launch_pair<1>(k, st));
-    else if (epl == 2) TRY(rr_launch_pair<2>(k, st));
-    else if (epl == 4) TRY(rr_launch_pair<4>(k, st));
+    if (c.epl == 1) TRY(rr_launch_pair<1>(k, st));
+    else if (c.epl == 2) TRY(rr_launch_pair<2>(k, st));
+    else if (c.epl == 4) TRY(rr_launch_pair<4>(k, st));
     else TRY(rr_launch_pair<8>(k, st));
-    TRY(enc_tail_forward(E, Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
-    if (!r.fuse) TRY(enc_final_ln_forward(E, Tt, ws, r.w, st));
+    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
+    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
     hipLaunchKernelGGL(rr_head_kernel, dim3(ps_cdiv((int64_t)B * r.tile, 4)), dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, B, r.tile,
                        k.nv, d, k.i0, k.ldS, S);
     PS_LAUNCH_CHECK();
@@ -554,4 +686,111 @@ extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shap
     PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)NP * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)NP * sizeof(float),
                                   (size_t)B, hipMemcpyDeviceToDevice, st));
   return rank_select_scores(S, r.ldS, B, NP, target_prod_idxs, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st);
+}
+
+// ------------------------------------------------------------------ per-entry candidate lists (ps_rtm_rank_cand_*, ps_rtm_rank_candidates)
+static int64_t rr_cand_default_tile(const PsRtmDesc& D, int64_t C) {
+  int64_t t = RR_PASS_PAIRS / D.B;
+  t = t < 1 ? 1 : t;
+  return t < C ? t : C;
+}
+// the pass size comes from the scratch, as rr_pass_layout takes it: the most columns of the list whose pairs fit
+static int rr_cand_pass_layout(const PsRtmDesc& D, int64_t C, int topk, int64_t scratch_bytes, RrWs& r) {
+  TRY(rr_cand_layout(D, C, topk, 1, r));
+  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_candidates: scratch %lld < %lld bytes (one candidate per pass)",
+             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
+  int64_t lo = 1, hi = C;
+  while ((int64_t)D.B * hi >= ((int64_t)1 << 30)) hi >>= 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    RrWs t;
+    if (rr_cand_layout(D, C, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
+  }
+  return rr_cand_layout(D, C, topk, lo, r);
+}
+
+extern "C" int64_t ps_rtm_rank_cand_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk,
+                                                  int64_t cands_per_pass) {
+  if (!desc || !shape) { ps_set_error("rtm rank_candidates scratch: null argument"); return -1; }
+  if (rr_check(*desc, *shape)) return -1;
+  int64_t tile = cands_per_pass > 0 ? cands_per_pass : rr_cand_default_tile(*desc, C);
+  if (tile > C && C >= 1) tile = C;
+  RrWs r;
+  if (rr_cand_layout(*desc, C, topk, tile, r)) return -1;
+  return r.total * (int64_t)sizeof(float);
+}
+
+extern "C" int ps_rtm_rank_cand_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk, int64_t scratch_bytes,
+                                     PsRtmRankCandPlan* out) {
+  PS_REQUIRE(desc && shape && out, "rtm rank_candidates plan: null argument");
+  memset(out, 0, sizeof(*out));
+  TRY(rr_check(*desc, *shape));
+  RrWs r;
+  TRY(rr_cand_pass_layout(*desc, C, topk, scratch_bytes, r));
+  out->cands_per_pass = r.tile;
+  out->passes = (C + r.tile - 1) / r.tile;
+  out->epl = rr_epl(*desc);
+  out->lph = rr_lph(*desc);
+  out->tail_fused = r.fuse ? 1 : 0;
+  out->query_fs_fused = rr_query_fs_fused(*desc) ? 1 : 0;
+  return PS_OK;
+}
+
+extern "C" int ps_rtm_rank_candidates(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
+                                      const int64_t* item_ridxs, const int64_t* query_word_idxs, const int64_t* u_ridxs,
+                                      const int64_t* candi_prod_idxs, int64_t C, const int64_t* target_prod_idxs, int32_t topk,
+                                      int64_t* top_idx, float* top_score, int32_t* rank, float* scores_out, void* scratch,
+                                      int64_t scratch_bytes, ps_stream_t stream) {
+  PS_REQUIRE(desc && shape && params && index && item_ridxs && query_word_idxs && u_ridxs && candi_prod_idxs && top_idx && top_score && scratch,
+             "rtm rank_candidates: null argument");
+  const PsRtmDesc& D = *desc;
+  const PsRtmRankShape& Sh = *shape;
+  const PsRtmTensors& P = *params;
+  TRY(rr_check(D, Sh));
+  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_candidates: rank needs target_prod_idxs");
+  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_candidates: scratch must be 256-byte aligned");
+  TRY(rr_tensor_check(D, P));
+  const int B = D.B, d = D.d;
+  RrWs r;
+  TRY(rr_cand_pass_layout(D, C, topk, scratch_bytes, r));
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = reinterpret_cast<float*>(scratch);
+  RrCall c;
+  TRY(rr_entry_side(D, Sh, P, index, item_ridxs, query_word_idxs, u_ridxs, r, ws, st, c));
+  RrK& k = c.k;
+  k.candi = candi_prod_idxs; k.C = (int)C;
+  // ---- passes over column tiles of the lists: candidate kernel -> the encoder's per-replica tail (n_in = B, fan = tile) -> head
+  float* S = ws + r.S;
+  const dim3 pg(ps_cdiv((int64_t)B * r.tile, 4));
+  for (int64_t c0 = 0; c0 < C; c0 += r.tile) {
+    k.i0 = (int)c0;
+    k.nv = (int)(c0 + r.tile <= C ? r.tile : C - c0);
+    {
+      KTimeScope kt("rtm_rank_cand", st);
+      if (c.epl == 1) PS_KLAUNCH((rr_cand_kernel<1>), pg, dim3(256), 0, st, k);
+      else if (c.epl == 2) PS_KLAUNCH((rr_cand_kernel<2>), pg, dim3(256), 0, st, k);
+      else if (c.epl == 4) PS_KLAUNCH((rr_cand_kernel<4>), pg, dim3(256), 0, st, k);
+      else PS_KLAUNCH((rr_cand_kernel<8>), pg, dim3(256), 0, st, k);
+      PS_LAUNCH_CHECK();
+    }
+    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
+    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
+    hipLaunchKernelGGL(rr_cand_head_kernel, pg, dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, candi_prod_idxs, B, r.tile, k.nv, d, k.i0,
+                       k.C, k.P, k.ldS, S);
+    PS_LAUNCH_CHECK();
+  }
+  if (scores_out)
+    PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)C * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)C * sizeof(float),
+                                  (size_t)B, hipMemcpyDeviceToDevice, st));
+  // ---- the selection is rank.hip's over [B, C] with the columns as ids: the target's column first, the columns -> item ids after
+  int64_t* tcol = reinterpret_cast<int64_t*>(ws + r.tcol);
+  if (target_prod_idxs) {
+    hipLaunchKernelGGL(rr_cand_target_kernel, dim3(ps_cdiv(B, 4)), dim3(256), 0, st, candi_prod_idxs, target_prod_idxs, B, (int)C, k.P, tcol);
+    PS_LAUNCH_CHECK();
+  }
+  TRY(rank_select_scores(S, r.ldS, B, C, target_prod_idxs ? tcol : nullptr, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st));
+  hipLaunchKernelGGL(rr_cand_ids_kernel, dim3(ps_cdiv((int64_t)B * topk, 256)), dim3(256), 0, st, candi_prod_idxs, B, (int)C, topk, top_idx,
+                     top_score);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
 }

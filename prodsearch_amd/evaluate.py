@@ -161,6 +161,54 @@ def rank_all_rtm(model, index, batch, topk=100, items_per_pass=None, return_scor
     return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
 
 
+def rank_candidates_rtm(model, index, batch, topk=100, cands_per_pass=None, return_scores=False):
+    """The review transformer over every entry's OWN candidate list (``ps_rtm_rank_candidates``): what
+    ``Trainer._scores_candidates`` gets from ``model.test`` over chunks of the lists plus its ranking chain — validation on
+    ``valid_candi_size`` sampled products, the rerank of ``test_candi_size`` lists.  ``index`` as for ``rank_all_rtm``;
+    ``batch`` a ``ProdSearchRankBatch`` with ``candi_prod_idxs`` [B, C] (item ids; a slot outside [0, P), the -1 padding of a
+    ragged list, is dead).  -> (top_idx [B,k] ITEM ids of the live slots by (score desc, column asc), -1 where unfilled;
+    top_score [B,k]; rank [B] int32: 1 + the live slots ahead of the first column holding the target, 0 = not in the list)
+    (+ the dense scores [B,C], -inf at dead slots, with ``return_scores``)."""
+    msg = model._rank_all_refusal()
+    if msg is not None:
+        raise NotImplementedError(msg)
+    if index.model is not model:
+        raise RuntimeError("rank_candidates_rtm: the catalogue index belongs to another model")
+    if index.stale():
+        raise RuntimeError("rank_candidates_rtm: stale catalogue index — a weight, a table or the catalogue changed since "
+                           "model.catalogue_index() built it; build it again")
+    if getattr(batch, 'candi_prod_idxs', None) is None:
+        raise RuntimeError("rank_candidates_rtm: the batch carries no candi_prod_idxs")
+    lib = _lib.load()
+    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
+    ur = model._idx(batch.u_ridxs, 'u_ridxs')
+    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
+    cand = model._idx(batch.candi_prod_idxs, 'candi_prod_idxs')
+    B, Q = qw.shape
+    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,) or cand.dim() != 2 or cand.shape[0] != B:
+        raise RuntimeError("rank_candidates_rtm: u_ridxs must be [B, U], target_prod_idxs [B] and candi_prod_idxs [B, C]")
+    ps, _ = model._structs()
+    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
+    k, C = int(topk), int(cand.shape[1])
+    dev = qw.device
+    nbytes = lib.ps_rtm_rank_cand_scratch_bytes(desc, sh, C, k, int(cands_per_pass or 0))
+    if nbytes < 0:
+        raise RuntimeError("rank_candidates_rtm: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
+    # exactly nbytes, as rank_all_rtm: the C entry sizes its passes from the scratch it is given
+    scratch = model.__dict__.get('_rtm_rank_cand_scratch')
+    if scratch is None or scratch.numel() != nbytes or scratch.device != dev:
+        scratch = model.__dict__['_rtm_rank_cand_scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, C, dtype=torch.float32, device=dev) if return_scores else None
+    _lib.check(lib.ps_rtm_rank_candidates(desc, sh, ps, index.index.data_ptr(), index.item_ridxs.data_ptr(), qw.data_ptr(),
+                                          ur.data_ptr(), cand.data_ptr(), C, target.data_ptr(), k, top_idx.data_ptr(),
+                                          top_score.data_ptr(), rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(),
+                                          scratch.numel(), torch.cuda.current_stream(dev).cuda_stream), 'ps_rtm_rank_candidates')
+    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+
+
 def calc_metrics(rank, cutoff=100):
     """``Trainer.calc_metrics`` (trainer.py:172-187) from the 1-based ranks of ``rank_all``."""
     r = torch.as_tensor(rank).detach().cpu().numpy().astype(np.int64)

@@ -81,19 +81,22 @@ class ProdSearchRankBatch(object):
         query_word_idxs   [B,Q]   pad V-1
         u_ridxs           [B,U]   the user's reviews (``get_user_review_idxs``), then the pad review
         target_prod_idxs  [B]     int64 tensor
+        candi_prod_idxs   [B,C]   optional: the entry's own candidate list (``evaluate.rank_candidates_rtm``), item ids,
+                                  a ragged list padded with -1
     """
-    def __init__(self, query_idxs, user_idxs, target_prod_idxs, query_word_idxs, u_ridxs):
+    def __init__(self, query_idxs, user_idxs, target_prod_idxs, query_word_idxs, u_ridxs, candi_prod_idxs=None):
         self.query_idxs, self.user_idxs = query_idxs, user_idxs
         self.target_prod_idxs = _t(target_prod_idxs)
         self.query_word_idxs = _t(query_word_idxs)
         self.u_ridxs = _t(u_ridxs)
+        self.candi_prod_idxs = _t(candi_prod_idxs)
 
     def to(self, device):
         if device == "cpu":
             return self
-        mv = lambda x: x.to(device, non_blocking=True)
+        mv = lambda x: None if x is None else x.to(device, non_blocking=True)
         return self.__class__(self.query_idxs, self.user_idxs, mv(self.target_prod_idxs), mv(self.query_word_idxs),
-                              mv(self.u_ridxs))
+                              mv(self.u_ridxs), mv(self.candi_prod_idxs))
 
 
 def make_review_words(seed, review_count, vocab_size, word_limit, word_dists=None):

@@ -299,10 +299,10 @@ class ProdSearchDataLoader(object):
         keep[1:] = (q[1:] != q[:-1]).any(1)
         return np.flatnonzero(keep)
 
-    def rank_batch_from_ids(self, ids):
+    def rank_batch_from_ids(self, ids, candi_prod_idxs=None):
         """Entries-only batch: the user's review ids as ``get_user_review_idxs(user, review, False, ..., fix=True)`` gives them
         (:64, 135-168: the user's TRAIN reviews other than the entry's, the last ``uprev_review_limit``), the query words and
-        the target."""
+        the target.  ``candi_prod_idxs`` [len(ids), C] (host): the entries' candidate lists, carried along."""
         self._rank_all_check()
         ids = np.asarray(ids, dtype=np.int64)
         quad = self.entry_quad[ids]
@@ -315,13 +315,34 @@ class ProdSearchDataLoader(object):
         qw = torch.from_numpy(np.ascontiguousarray(c.query_words[quad[:, 0]]))
         return ProdSearchRankBatch(quad[:, 0].tolist(), quad[:, 1].tolist(),
                                    self._ship(torch.from_numpy(np.ascontiguousarray(quad[:, 2]))), self._ship(qw),
-                                   self._ship(torch.from_numpy(u_r)))
+                                   self._ship(torch.from_numpy(u_r)),
+                                   None if candi_prod_idxs is None else self._ship(torch.from_numpy(candi_prod_idxs)))
 
     def rank_batches(self):
         """The dataset's distinct entries, ``batch_size`` at a time."""
         ent = self.rank_entries()
         for lo in range(0, len(ent), self.batch_size):
             yield self.rank_batch_from_ids(ent[lo:lo + self.batch_size])
+
+    def candidate_lists(self, ent=None):
+        """Per distinct entry (``rank_entries()``, or the positions ``ent`` of them): the candidate chunks of its consecutive
+        dataset rows (prod_search_dataset.py:62-74) concatenated in dataset order."""
+        first = self.rank_entries()
+        end = np.append(first[1:], len(self.entry_quad))
+        pick = range(len(first)) if ent is None else ent
+        return [self.candi_items[self.candi_ptr[first[j]]:self.candi_ptr[end[j]]] for j in pick]
+
+    def candidate_batches(self):
+        """The dataset's distinct entries with their own candidate lists (``evaluate.rank_candidates_rtm``), ``batch_size`` at
+        a time: ``candi_prod_idxs`` [B, C] padded with -1 to the batch's widest list."""
+        self._rank_all_check()
+        ent = self.rank_entries()
+        for lo in range(0, len(ent), self.batch_size):
+            lists = self.candidate_lists(range(lo, min(lo + self.batch_size, len(ent))))
+            cand = np.full((len(lists), max(1, max(len(x) for x in lists))), -1, dtype=np.int64)
+            for b, x in enumerate(lists):
+                cand[b, :len(x)] = x
+            yield self.rank_batch_from_ids(ent[lo:lo + self.batch_size], cand)
 
     # ------------------------------------------------------------------ the reference's collate_fn entry points
     def get_train_batch(self, batch):

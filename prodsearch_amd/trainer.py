@@ -10,7 +10,8 @@ validation MRR and the same TREC-style ranklist (``trainer.py:160-170``).  MI355
   (the reference calls ``.item()`` three times per step);
 * evaluation over all products (``*_candi_size < 1``) is ``evaluate.rank_all`` (one encode per row, scores and top-k
   on the device); sampled-candidate validation goes through ``model.test`` like the reference.  The review transformer
-  goes through ``model.test`` over candidate chunks, or with ``args.rtm_rank_all`` through ``evaluate.rank_all_rtm``.
+  goes through ``model.test`` over candidate chunks, or with ``args.rtm_rank_all`` through ``evaluate.rank_all_rtm``
+  (all products) / ``evaluate.rank_candidates_rtm`` (candidate lists: sampled validation, the rerank of ``test_candi_size``).
 """
 import logging
 import os
@@ -199,9 +200,27 @@ class Trainer(object):
             self.model.clear_review_embbeddings()
         return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
 
+    def _scores_rank_cand_rtm(self, args, global_data, dataset, topk):
+        """``args.rtm_rank_all`` with candidate lists: every entry's own list in one pass per batch of entries
+        (``evaluate.rank_candidates_rtm``); returns what ``_scores_candidates(..., topk=topk)`` returns."""
+        loader = self.ExpDataloader(args, dataset, batch_size=args.valid_batch_size, shuffle=False, device=args.device)
+        tops, scores, ranks, users, queries = [], [], [], [], []
+        self.model.eval()
+        with torch.no_grad():
+            up = global_data.review_u_p if (args.use_user_emb or args.use_item_emb) else None
+            index = self.model.catalogue_index(loader.catalogue_reviews(), up)
+            for b in loader.candidate_batches():
+                ti, ts, rk = evaluate.rank_candidates_rtm(self.model, index, b, topk)
+                tops.append(ti); scores.append(ts); ranks.append(rk.to(torch.int64))
+                users += list(b.user_idxs); queries += list(b.query_idxs)
+            self.model.clear_review_embbeddings()
+        return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
+
     def validate(self, args, global_data, valid_dataset):
         if self.rtm and getattr(args, 'rtm_rank_all', False) and args.valid_candi_size < 1:
             return evaluate.calc_metrics(self._scores_rank_all_rtm(args, global_data, valid_dataset, 1)[0], 100)
+        if self.rtm and getattr(args, 'rtm_rank_all', False):
+            return evaluate.calc_metrics(self._scores_rank_cand_rtm(args, global_data, valid_dataset, 1)[0], 100)
         if self.rtm:
             size = args.valid_candi_size if args.valid_candi_size >= 1 else global_data.product_size   # trainer.py:127-129
             return evaluate.calc_metrics(self._scores_candidates(args, valid_dataset, size), 100)
@@ -217,6 +236,9 @@ class Trainer(object):
         if self.rtm and getattr(args, 'rtm_rank_all', False) and args.test_candi_size < 1:
             rank, top_idx, top_score, users, queries = self._scores_rank_all_rtm(
                 args, global_data, dataset, min(cutoff, global_data.product_size, 256))
+        elif self.rtm and getattr(args, 'rtm_rank_all', False):
+            rank, top_idx, top_score, users, queries = self._scores_rank_cand_rtm(
+                args, global_data, dataset, min(cutoff, args.test_candi_size, 256))
         elif self.rtm:
             size = args.test_candi_size if args.test_candi_size >= 1 else global_data.product_size     # trainer.py:141-143
             rank, top_idx, top_score, users, queries = self._scores_candidates(args, dataset, size, topk=min(cutoff, size))

@@ -36,7 +36,7 @@ from prodsearch_amd import ProductRanker, _lib, default_args, evaluate, rtm_data
 U, I, WL, d, H, V, RC, CHUNK = 20, 30, 100, 128, 8, 32387, 296000, 500
 
 
-def build(P, B):
+def build(P, B, with_chunks=True):
     a = default_args(model_name='review_transformer', review_encoder_name='pvc', embedding_size=d, heads=H, ff_size=512,
                      inter_layers=1, dropout=0.1, corrupt_rate=0.9, review_word_limit=WL, uprev_review_limit=U,
                      iprev_review_limit=I, candi_batch_size=CHUNK)
@@ -64,7 +64,7 @@ def build(P, B):
     R = U + I
     pos = torch.arange(R)[None, None, :]
     chunks = []
-    for lo in range(0, P, CHUNK):
+    for lo in range(0, P if with_chunks else 0, CHUNK):      # (tools/bench_rtm_cand.py assembles its own chunk)
         ids = torch.arange(lo, min(P, lo + CHUNK))
         from_u = pos < nu[:, None, None]
         j = (pos - nu[:, None, None]).clamp(0, I - 1).expand(B, len(ids), R)
