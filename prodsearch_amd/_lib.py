@@ -138,6 +138,17 @@ class PsRtmRankCandPlan(C.Structure):
                [(n, C.c_int32) for n in ('epl', 'lph', 'tail_fused', 'query_fs_fused')]
 
 
+class PsRtmSeqTimeline(C.Structure):
+    _fields_ = [('ptr', C.c_void_p), ('rids', C.c_void_p), ('times', C.c_void_p), ('n', C.c_int64)]
+
+
+class PsRtmRankSeqPlan(C.Structure):
+    _fields_ = [('slots_per_pass', C.c_int64), ('passes', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('epl', 'lph', 'tail_fused', 'query_fs_fused')]
+
+
+PS_RTM_SEQ_NO_LIST = -1
+
 # every symbol include/prodsearch_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     'ps_version': (C.c_char_p, []),
@@ -285,6 +296,16 @@ RANK_CAND_SYMBOLS = {
                                [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
 }
 
+# include/prodsearch_rtm_seq.h (the HIP library as well)
+RANK_SEQ_SYMBOLS = {
+    'ps_rtm_rank_seq_scratch_bytes': (C.c_int64, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int64, C.c_int32, C.c_int64]),
+    'ps_rtm_rank_seq_plan': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.c_int64, C.c_int32, C.c_int64,
+                                       C.POINTER(PsRtmRankSeqPlan)]),
+    'ps_rtm_rank_seq': (C.c_int, [C.POINTER(PsRtmDesc), C.POINTER(PsRtmRankShape), C.POINTER(PsRtmTensors), C.c_void_p,
+                                  C.POINTER(PsRtmSeqTimeline)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int32] +
+                        [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+}
+
 # include/prodsearch_data.h (host-only library)
 DATA_SYMBOLS = {
     'ps_rtm_collate_train': (C.c_int, [C.POINTER(PsRtmCorpusView), C.POINTER(PsRtmCollateArgs), C.c_void_p, C.c_void_p,
@@ -360,7 +381,7 @@ def load():
         raise RuntimeError("libprodsearch_hip.so not found at %s: run `python -m prodsearch_amd.build` "
                            "(there is no CPU fallback)" % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(RANK_CAND_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(RANK_CAND_SYMBOLS.items()) + list(RANK_SEQ_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library drift
         fn.restype = res
         fn.argtypes = args

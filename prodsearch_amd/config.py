@@ -76,7 +76,7 @@ _DEFAULTS = dict(
     start_epoch=0,
     steps_per_checkpoint=200,
     materialize_candidates=False,      # extension: build the reference's chunked all-product candidate lists
-    rtm_rank_all=False,                # extension: review transformer evaluation in one pass: the catalogue with *_candi_size < 1 (evaluate.rank_all_rtm), else the entries' candidate lists (evaluate.rank_candidates_rtm)
+    rtm_rank_all=False,                # extension: review transformer evaluation in one pass: the catalogue with *_candi_size < 1 (evaluate.rank_all_rtm), else the entries' candidate lists (evaluate.rank_candidates_rtm); with do_seq_review_test and not train_review_only both through evaluate.rank_seq_rtm
 )
 
 

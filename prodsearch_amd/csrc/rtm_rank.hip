@@ -21,9 +21,14 @@
 //   rr_cand                per (entry, slot of its list): one wave per pair, the K / V rows straight from KR / VR — no LDS tile,
 //                          two entries' lists have no item in common; the same rr_step in the same order as rr_pair
 //   rr_cand_head / _target / _ids   scores [B, C] (-inf at dead slots), the target's column, the selected columns -> item ids
+// The TIME-ORDERED evaluation (include/prodsearch_rtm_seq.h, ps_rtm_rank_seq*: do_seq_review_test without
+// train_review_only) keeps the index and the entry side too; what changes is which review ids a pair reads:
+//   rr_seq                 per (entry, slot): the item's time-ordered sequence is searched wave-wide for the entry's time stamp and the
+//                          iprev_review_limit reviews just before the cut are the pair's list; the walk after that is rr_cand's
 // fp32 throughout, plain C++; the per-pair tail is the encoder's own (enc_tail_forward).
 #include "rtm.h"
 #include "../../include/prodsearch_rtm_cand.h"
+#include "../../include/prodsearch_rtm_seq.h"
 #include "rank.h"
 #include "wgrad.h"      // gp / run1
 #include <math.h>
@@ -134,6 +139,7 @@ struct RrK {
   float *em, *es, *eacc; int32_t* entn;
   float* ctx;
   const int64_t* candi; int C;         // rr_cand_kernel: the lists [B, C]; i0 is then the pass's first column
+  const int64_t *tl_ptr, *tl_rids, *tl_times, *stamps; int64_t tl_n;   // rr_seq_kernel: the timeline (CSR + times) and the entries' stamps [B]
 };
 
 // T[r] = rev[r] (+ user_emb[author]) (+ product_emb[item]) with the id rule of rtm_embed_kernel: an id outside [0, pad] adds nothing
@@ -344,6 +350,86 @@ __global__ __launch_bounds__(256) void rr_cand_kernel(const RrK a) {
   int64_t gi = a.candi[(size_t)e * a.C + c];
   gi = (gi < 0 || gi >= a.P) ? 0 : gi;
   const int id = lane < a.I ? (int)rclamp(a.item_r[(size_t)gi * a.I + lane], a.RC - 1) : pad;
+  const int nu = a.entn[e];
+  int n = rr_leading(id, pad);
+  n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;        // the sequence never exceeds 1 + total_review_limit positions
+  const size_t col = (size_t)lane * EPL;
+  const float* kt2 = a.kt + (size_t)a.T1 * d;
+  const float* vt2 = a.vt + (size_t)a.T1 * d;
+  float q[EPL], k[RR_U][EPL], v[RR_U][EPL], acc[EPL];
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) { q[i] = a.qp[(size_t)e * d + col + i]; acc[i] = a.eacc[(size_t)e * d + col + i]; }
+  float m = a.em[(size_t)e * 64 + lane], s = a.es[(size_t)e * 64 + lane];
+  for (int j = 0; j < n; j += RR_U) {
+#pragma unroll
+    for (int u = 0; u < RR_U; ++u) {
+      const int jj = j + u < n ? j + u : n - 1;     // (a slot past the list repeats its last row; rr_step drops it)
+      const size_t r = (size_t)__shfl(id, jj, 64);
+      const size_t pos = (size_t)(1 + nu + jj) * d + col;
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) {
+        k[u][i] = a.KR[r * d + col + i] + kt2[pos + i];
+        v[u][i] = a.VR[r * d + col + i] + vt2[pos + i];
+      }
+    }
+    rr_step<EPL>(q, k, v, n - j, a.lph, m, s, acc);
+  }
+  const float inv = 1.f / s;
+  float* out = a.ctx + ((size_t)e * a.tile + t) * d + col;
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) out[i] = acc[i] * inv;
+}
+
+// per (entry, slot) in the time-ordered evaluation (do_seq_review_test without train_review_only, prod_search_dataloader.py:60-77,
+// 138-147): the pair's list is not a fixed [P, I] row but the I reviews of the item just before a cut in the item's time-ordered
+// sequence, cut = bisect_right(times of the sequence, the entry's stamp).  One wave per pair as rr_cand_kernel; with a list (candi)
+// the item is the slot's, a dead slot computed on item 0; without one it is catalogue row min(i0 + t, P - 1).
+// The search is wave-wide: each round the 64 lanes probe 64 evenly spaced elements of the open range, one ballot of time <= stamp and
+// its population count leave the stretch between two probes: one round up to 64 reviews, two up to 4,160, three up to 266,304.
+// Every load of the search and of the window is unconditional on an index clamped into [0, N - 1] (N >= 1); what a lane may use of
+// it is decided afterwards.  From the window on the code is rr_cand_kernel's: the same rr_step on the same operands in the same
+// groups, so a pair's bits are those of the static kernels on the same list.
+template <int EPL>
+__global__ __launch_bounds__(256) void rr_seq_kernel(const RrK a) {
+  const int lane = threadIdx.x & 63;
+  const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  if (p >= a.B * a.tile) return;                    // (wave-uniform)
+  const int e = p / a.tile, t = p - e * a.tile;
+  const int d = a.d, pad = (int)(a.RC - 1);
+  int64_t gi;
+  if (a.candi) {                                    // (wave-uniform)
+    int c = a.i0 + t;
+    c = c < a.C ? c : a.C - 1;
+    gi = a.candi[(size_t)e * a.C + c];
+    gi = (gi < 0 || gi >= a.P) ? 0 : gi;
+  } else {
+    gi = a.i0 + t;
+    gi = gi < a.P ? gi : a.P - 1;
+  }
+  const int64_t stamp = a.stamps[e], last = a.tl_n - 1;
+  int64_t lo = a.tl_ptr[gi], hi = a.tl_ptr[gi + 1];
+  lo = lo < 0 ? 0 : (lo > a.tl_n ? a.tl_n : lo);    // (a corrupt ptr cannot send a load outside the arrays)
+  hi = hi < lo ? lo : (hi > a.tl_n ? a.tl_n : hi);
+  // the cut lies in [b0, b1]: every element before b0 is <= stamp, every element from b1 on is greater
+  int64_t b0 = lo, b1 = hi;
+  while (b1 > b0) {                                 // (wave-uniform: b0 / b1 come from ballots)
+    const int64_t len = b1 - b0, step = (len + 63) >> 6;
+    const int64_t off = (int64_t)lane * step;
+    int64_t ix = b0 + off;
+    ix = ix < last ? ix : last;
+    const bool le = a.tl_times[ix] <= stamp && off < len;
+    const int c = __popcll(__ballot(le));            // the probes are in time order: the first c of them hold
+    if (c == 0) { b1 = b0; break; }
+    const int64_t nb1 = b0 + (int64_t)c * step;
+    b0 = b0 + (int64_t)(c - 1) * step + 1;
+    b1 = nb1 < b1 ? nb1 : b1;
+  }
+  const int64_t cut = b0 - lo;
+  const int nraw = (int)(cut < a.I ? cut : a.I);
+  int64_t wx = b0 - nraw + lane;
+  wx = wx < 0 ? 0 : (wx < last ? wx : last);
+  const int rid = (int)rclamp(a.tl_rids[wx], a.RC - 1);
+  const int id = lane < nraw ? rid : pad;
   const int nu = a.entn[e];
   int n = rr_leading(id, pad);
   n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;        // the sequence never exceeds 1 + total_review_limit positions
@@ -783,6 +869,137 @@ extern "C" int ps_rtm_rank_candidates(const PsRtmDesc* desc, const PsRtmRankShap
     PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)C * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)C * sizeof(float),
                                   (size_t)B, hipMemcpyDeviceToDevice, st));
   // ---- the selection is rank.hip's over [B, C] with the columns as ids: the target's column first, the columns -> item ids after
+  int64_t* tcol = reinterpret_cast<int64_t*>(ws + r.tcol);
+  if (target_prod_idxs) {
+    hipLaunchKernelGGL(rr_cand_target_kernel, dim3(ps_cdiv(B, 4)), dim3(256), 0, st, candi_prod_idxs, target_prod_idxs, B, (int)C, k.P, tcol);
+    PS_LAUNCH_CHECK();
+  }
+  TRY(rank_select_scores(S, r.ldS, B, C, target_prod_idxs ? tcol : nullptr, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st));
+  hipLaunchKernelGGL(rr_cand_ids_kernel, dim3(ps_cdiv((int64_t)B * topk, 256)), dim3(256), 0, st, candi_prod_idxs, B, (int)C, topk, top_idx,
+                     top_score);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// ------------------------------------------------------------------ the time-ordered evaluation (ps_rtm_rank_seq*)
+// The columns are the slots of the entries' lists (C of them) or, with no list, the P catalogue rows.  The shape's seq_review_test
+// says what the run is and is not a refusal here: rr_check sees the shape with the field cleared.
+static PsRtmRankShape rr_seq_shape(const PsRtmRankShape& S) { PsRtmRankShape s = S; s.seq_review_test = 0; return s; }
+static int rr_seq_layout(const PsRtmDesc& D, int64_t cols, bool list, int topk, int64_t tile, RrWs& r) {
+  PS_REQUIRE(!list || cols >= 1, "rtm rank_seq: %lld candidates per entry (at least 1)", (long long)cols);
+  PS_REQUIRE(cols >= 1 && cols < ((int64_t)1 << 31), "rtm rank_seq: %lld columns", (long long)cols);
+  PS_REQUIRE(tile >= 1 && tile <= cols && (int64_t)D.B * tile < ((int64_t)1 << 30), "rtm rank_seq: %lld slots per pass", (long long)tile);
+  TRY(rr_layout_cols(D, cols, topk, tile, "rtm rank_seq", r));
+  int64_t cur = r.total;
+  r.tcol = rtake(cur, 2 * (int64_t)D.B);
+  r.total = cur;
+  return PS_OK;
+}
+static int rr_seq_pass_layout(const PsRtmDesc& D, int64_t cols, bool list, int topk, int64_t scratch_bytes, RrWs& r) {
+  TRY(rr_seq_layout(D, cols, list, topk, 1, r));
+  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_seq: scratch %lld < %lld bytes (one slot per pass)",
+             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
+  int64_t lo = 1, hi = cols;
+  while ((int64_t)D.B * hi >= ((int64_t)1 << 30)) hi >>= 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    RrWs t;
+    if (rr_seq_layout(D, cols, list, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
+  }
+  return rr_seq_layout(D, cols, list, topk, lo, r);
+}
+// (the host-only entries have no list pointer to look at: C = PS_RTM_SEQ_NO_LIST names the catalogue form there)
+static int64_t rr_seq_cols(const PsRtmRankShape& S, int64_t C, bool list) { return list ? C : S.n_items; }
+
+extern "C" int64_t ps_rtm_rank_seq_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk,
+                                                 int64_t slots_per_pass) {
+  if (!desc || !shape) { ps_set_error("rtm rank_seq scratch: null argument"); return -1; }
+  const PsRtmRankShape Sh = rr_seq_shape(*shape);
+  if (rr_check(*desc, Sh)) return -1;
+  const bool list = C != PS_RTM_SEQ_NO_LIST;
+  const int64_t cols = rr_seq_cols(Sh, C, list);
+  int64_t tile = slots_per_pass > 0 ? slots_per_pass : rr_cand_default_tile(*desc, cols);
+  if (tile > cols && cols >= 1) tile = cols;
+  RrWs r;
+  if (rr_seq_layout(*desc, cols, list, topk, tile, r)) return -1;
+  return r.total * (int64_t)sizeof(float);
+}
+
+extern "C" int ps_rtm_rank_seq_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk, int64_t scratch_bytes,
+                                    PsRtmRankSeqPlan* out) {
+  PS_REQUIRE(desc && shape && out, "rtm rank_seq plan: null argument");
+  memset(out, 0, sizeof(*out));
+  const PsRtmRankShape Sh = rr_seq_shape(*shape);
+  TRY(rr_check(*desc, Sh));
+  const bool list = C != PS_RTM_SEQ_NO_LIST;
+  const int64_t cols = rr_seq_cols(Sh, C, list);
+  RrWs r;
+  TRY(rr_seq_pass_layout(*desc, cols, list, topk, scratch_bytes, r));
+  out->slots_per_pass = r.tile;
+  out->passes = (cols + r.tile - 1) / r.tile;
+  out->epl = rr_epl(*desc);
+  out->lph = rr_lph(*desc);
+  out->tail_fused = r.fuse ? 1 : 0;
+  out->query_fs_fused = rr_query_fs_fused(*desc) ? 1 : 0;
+  return PS_OK;
+}
+
+extern "C" int ps_rtm_rank_seq(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
+                               const PsRtmSeqTimeline* timeline, const int64_t* query_word_idxs, const int64_t* u_ridxs,
+                               const int64_t* time_stamps, const int64_t* candi_prod_idxs, int64_t C, const int64_t* target_prod_idxs,
+                               int32_t topk, int64_t* top_idx, float* top_score, int32_t* rank, float* scores_out, void* scratch,
+                               int64_t scratch_bytes, ps_stream_t stream) {
+  PS_REQUIRE(desc && shape && params && index && query_word_idxs && u_ridxs && time_stamps && top_idx && top_score && scratch,
+             "rtm rank_seq: null argument");
+  PS_REQUIRE(timeline && timeline->ptr && timeline->rids && timeline->times, "rtm rank_seq: null timeline");
+  PS_REQUIRE(timeline->n >= 1, "rtm rank_seq: a timeline of %lld reviews (at least 1)", (long long)timeline->n);
+  const PsRtmDesc& D = *desc;
+  const PsRtmRankShape Sh = rr_seq_shape(*shape);
+  const PsRtmTensors& P = *params;
+  TRY(rr_check(D, Sh));
+  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_seq: rank needs target_prod_idxs");
+  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_seq: scratch must be 256-byte aligned");
+  TRY(rr_tensor_check(D, P));
+  const bool list = candi_prod_idxs != nullptr;
+  const int B = D.B, d = D.d;
+  const int64_t cols = rr_seq_cols(Sh, C, list);
+  RrWs r;
+  TRY(rr_seq_pass_layout(D, cols, list, topk, scratch_bytes, r));
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = reinterpret_cast<float*>(scratch);
+  RrCall c;
+  TRY(rr_entry_side(D, Sh, P, index, nullptr, query_word_idxs, u_ridxs, r, ws, st, c));
+  RrK& k = c.k;
+  k.candi = candi_prod_idxs; k.C = list ? (int)C : 0;
+  k.tl_ptr = timeline->ptr; k.tl_rids = timeline->rids; k.tl_times = timeline->times; k.tl_n = timeline->n; k.stamps = time_stamps;
+  // ---- passes over column tiles: window + walk -> the encoder's per-replica tail (n_in = B, fan = tile) -> head
+  float* S = ws + r.S;
+  const dim3 pg(ps_cdiv((int64_t)B * r.tile, 4));
+  for (int64_t c0 = 0; c0 < cols; c0 += r.tile) {
+    k.i0 = (int)c0;
+    k.nv = (int)(c0 + r.tile <= cols ? r.tile : cols - c0);
+    {
+      KTimeScope kt("rtm_rank_seq", st);
+      if (c.epl == 1) PS_KLAUNCH((rr_seq_kernel<1>), pg, dim3(256), 0, st, k);
+      else if (c.epl == 2) PS_KLAUNCH((rr_seq_kernel<2>), pg, dim3(256), 0, st, k);
+      else if (c.epl == 4) PS_KLAUNCH((rr_seq_kernel<4>), pg, dim3(256), 0, st, k);
+      else PS_KLAUNCH((rr_seq_kernel<8>), pg, dim3(256), 0, st, k);
+      PS_LAUNCH_CHECK();
+    }
+    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
+    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
+    if (list)
+      hipLaunchKernelGGL(rr_cand_head_kernel, pg, dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, candi_prod_idxs, B, r.tile, k.nv, d, k.i0,
+                         k.C, k.P, k.ldS, S);
+    else
+      hipLaunchKernelGGL(rr_head_kernel, pg, dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, B, r.tile, k.nv, d, k.i0, k.ldS, S);
+    PS_LAUNCH_CHECK();
+  }
+  if (scores_out)
+    PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)cols * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)cols * sizeof(float),
+                                  (size_t)B, hipMemcpyDeviceToDevice, st));
+  // ---- the selection: ps_rtm_rank_all's over the catalogue rows, ps_rtm_rank_candidates' over the columns of the lists
+  if (!list) return rank_select_scores(S, r.ldS, B, cols, target_prod_idxs, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st);
   int64_t* tcol = reinterpret_cast<int64_t*>(ws + r.tcol);
   if (target_prod_idxs) {
     hipLaunchKernelGGL(rr_cand_target_kernel, dim3(ps_cdiv(B, 4)), dim3(256), 0, st, candi_prod_idxs, target_prod_idxs, B, (int)C, k.P, tcol);

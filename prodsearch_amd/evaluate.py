@@ -209,6 +209,57 @@ def rank_candidates_rtm(model, index, batch, topk=100, cands_per_pass=None, retu
     return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
 
 
+def rank_seq_rtm(model, index, batch, topk=100, slots_per_pass=None, return_scores=False):
+    """The review transformer's one-pass evaluation in the TIME-ORDERED setting (``ps_rtm_rank_seq``, DESIGN.md §8b.3:
+    ``do_seq_review_test`` without ``train_review_only``): a pair reads the ``iprev_review_limit`` reviews of its item written
+    up to the entry's time stamp.  ``index`` = ``model.timeline_index(*loader.timeline(), review_u_p)``; ``batch`` a
+    ``ProdSearchRankBatch`` with ``time_stamps`` [B] (``ProdSearchDataLoader.seq_rank_batches`` / ``seq_candidate_batches``).
+    With ``candi_prod_idxs`` [B, C] the result is ``rank_candidates_rtm``'s over the lists, without them ``rank_all_rtm``'s
+    over the catalogue (+ the dense scores [B, C] / [B, P] with ``return_scores``)."""
+    msg = model._rank_all_refusal(time_ordered=True)
+    if msg is not None:
+        raise NotImplementedError(msg)
+    if index.model is not model:
+        raise RuntimeError("rank_seq_rtm: the timeline index belongs to another model")
+    if index.stale():
+        raise RuntimeError("rank_seq_rtm: stale timeline index — a weight, a table or the timeline changed since "
+                           "model.timeline_index() built it; build it again")
+    if getattr(batch, 'time_stamps', None) is None:
+        raise RuntimeError("rank_seq_rtm: the batch carries no time_stamps")
+    lib = _lib.load()
+    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
+    ur = model._idx(batch.u_ridxs, 'u_ridxs')
+    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
+    stamps = model._idx(batch.time_stamps, 'time_stamps')
+    cand = model._idx(getattr(batch, 'candi_prod_idxs', None), 'candi_prod_idxs')
+    B, Q = qw.shape
+    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,) or stamps.shape != (B,) or \
+            (cand is not None and (cand.dim() != 2 or cand.shape[0] != B)):
+        raise RuntimeError("rank_seq_rtm: u_ridxs must be [B, U], target_prod_idxs and time_stamps [B], candi_prod_idxs [B, C]")
+    ps, _ = model._structs()
+    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
+    P = index.shape3[0]
+    k, C = int(topk), (_lib.PS_RTM_SEQ_NO_LIST if cand is None else int(cand.shape[1]))
+    dev = qw.device
+    nbytes = lib.ps_rtm_rank_seq_scratch_bytes(desc, sh, C, k, int(slots_per_pass or 0))
+    if nbytes < 0:
+        raise RuntimeError("rank_seq_rtm: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
+    # exactly nbytes, as rank_all_rtm: the C entry sizes its passes from the scratch it is given
+    scratch = model.__dict__.get('_rtm_rank_seq_scratch')
+    if scratch is None or scratch.numel() != nbytes or scratch.device != dev:
+        scratch = model.__dict__['_rtm_rank_seq_scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tl = _lib.PsRtmSeqTimeline(index.ptr.data_ptr(), index.rids.data_ptr(), index.times.data_ptr(), index.rids.numel())
+    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, P if cand is None else C, dtype=torch.float32, device=dev) if return_scores else None
+    _lib.check(lib.ps_rtm_rank_seq(desc, sh, ps, index.index.data_ptr(), tl, qw.data_ptr(), ur.data_ptr(), stamps.data_ptr(),
+                                   _lib.ptr(cand), max(C, 0), target.data_ptr(), k, top_idx.data_ptr(), top_score.data_ptr(),
+                                   rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(), scratch.numel(),
+                                   torch.cuda.current_stream(dev).cuda_stream), 'ps_rtm_rank_seq')
+    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+
+
 def calc_metrics(rank, cutoff=100):
     """``Trainer.calc_metrics`` (trainer.py:172-187) from the 1-based ranks of ``rank_all``."""
     r = torch.as_tensor(rank).detach().cpu().numpy().astype(np.int64)

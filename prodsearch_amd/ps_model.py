@@ -51,6 +51,16 @@ class _CatalogueIndex(object):
         return self.model._rank_all_stamp(self.item_ridxs, self.review_u_p, self.table) != self.stamp
 
 
+class _TimelineIndex(object):
+    """What ``ProductRanker.timeline_index`` returns: the projection (the one ``catalogue_index`` builds: it holds no review
+    list) and the time-ordered CSR it serves — ``ptr`` [P + 1], ``rids`` / ``times`` [N] on the device."""
+    __slots__ = ('model', 'index', 'ptr', 'rids', 'times', 'review_u_p', 'shape3', 'stamp', 'table')
+
+    def stale(self):
+        """``_CatalogueIndex.stale`` with the timeline's three arrays in the catalogue's place."""
+        return self.model._rank_all_stamp(self.ptr, self.rids, self.times, self.review_u_p, self.table) != self.stamp
+
+
 class ProductRanker(HotPathModule):
     def __init__(self, args, device, vocab_size, review_count, product_size, user_size,
                  review_words, vocab_words, word_dists=None):
@@ -170,14 +180,15 @@ class ProductRanker(HotPathModule):
         self.__dict__['_rev_emb_stamp'] = self._rank_all_stamp()      # (catalogue_index: is this table still the weights'?)
 
     # ------------------------------------------------------- the whole catalogue in one pass (evaluate.rank_all_rtm)
-    def _rank_all_refusal(self):
+    def _rank_all_refusal(self, time_ordered=False):
         """Why ``catalogue_index`` / ``rank_all_rtm`` cannot serve this configuration (the message names the flag), or None.
-        ``PretrainedProductRanker`` is served: it inherits ``test``, which reads the same ``review_embeddings`` table."""
+        ``PretrainedProductRanker`` is served: it inherits ``test``, which reads the same ``review_embeddings`` table.
+        ``time_ordered``: asked by ``timeline_index`` / ``rank_seq_rtm``, which serve the time-ordered mode as well."""
         a = self.args
         if a.inter_layers != 1:
             return ("rank_all_rtm: inter_layers = %d — one encoder layer is built (deeper encoders need every position of "
                     "layer 0)" % a.inter_layers)
-        if getattr(a, 'do_seq_review_test', False) and not a.train_review_only:
+        if not time_ordered and getattr(a, 'do_seq_review_test', False) and not a.train_review_only:
             return ("rank_all_rtm: do_seq_review_test without train_review_only — an item's review list then depends on "
                     "the entry")
         if self.fix_emb and self.review_encoder_name in ('fs', 'avg'):
@@ -214,33 +225,49 @@ class ProductRanker(HotPathModule):
         msg = self._rank_all_refusal()
         if msg is not None:
             raise NotImplementedError(msg)
-        lib = _lib.load()
         item_ridxs = self._idx(item_ridxs, 'item_ridxs')
         if item_ridxs.dim() != 2:
             raise RuntimeError("item_ridxs must be [P, I]")
-        need_up = self.use_user_emb or self.use_item_emb
-        if need_up:
-            if review_u_p is None:
-                raise RuntimeError("use_user_emb / use_item_emb: catalogue_index needs review_u_p")
-            review_u_p = torch.as_tensor(np.asarray(review_u_p), dtype=torch.int64).reshape(-1, 2) \
-                if not torch.is_tensor(review_u_p) else review_u_p
-            review_u_p = self._idx(review_u_p.to(self._dev()), 'review_u_p')
-        else:
-            review_u_p = None
-        # the review table the projection reads: a pvc / fs / avg table computed from weights that have changed since (an
-        # optimizer step without clear_review_embbeddings()) is computed again; pv / fix_emb: the parameter itself
+        review_u_p = self._rank_review_u_p(review_u_p, 'catalogue_index')
+        self._rank_review_table()
+        stamp = self._rank_all_stamp(item_ridxs, review_u_p, self.review_embeddings)
+        cached = self.__dict__.get('_cat_index')
+        if cached is not None and cached.stamp == stamp:
+            return cached
+        shape3 = (item_ridxs.shape[0], 0 if review_u_p is None else review_u_p.shape[0], item_ridxs.shape[1])
+        out = self._rank_project(shape3, review_u_p)
+        idx = _CatalogueIndex()
+        idx.model, idx.index, idx.item_ridxs, idx.review_u_p, idx.shape3, idx.stamp = self, out, item_ridxs, review_u_p, shape3, stamp
+        idx.table = self.review_embeddings
+        self.__dict__['_cat_index'] = idx
+        return idx
+
+    def _rank_review_u_p(self, review_u_p, who):
+        """``review_u_p`` [n_reviews, 2] on the device where ``use_user_emb`` / ``use_item_emb`` read it, else None."""
+        if not (self.use_user_emb or self.use_item_emb):
+            return None
+        if review_u_p is None:
+            raise RuntimeError("use_user_emb / use_item_emb: %s needs review_u_p" % who)
+        review_u_p = torch.as_tensor(np.asarray(review_u_p), dtype=torch.int64).reshape(-1, 2) \
+            if not torch.is_tensor(review_u_p) else review_u_p
+        return self._idx(review_u_p.to(self._dev()), 'review_u_p')
+
+    def _rank_review_table(self):
+        """The review table the projection reads: a pvc / fs / avg table computed from weights that have changed since (an
+        optimizer step without clear_review_embbeddings()) is computed again; pv / fix_emb: the parameter itself."""
         if self.review_embeddings is not None and self.review_encoder_name != 'pv' and \
                 self.__dict__.get('_rev_emb_stamp') != self._rank_all_stamp():
             self.review_embeddings = None
         if self.review_embeddings is None:
             self.get_review_embeddings()
-        stamp = self._rank_all_stamp(item_ridxs, review_u_p, self.review_embeddings)
-        cached = self.__dict__.get('_cat_index')
-        if cached is not None and cached.stamp == stamp:
-            return cached
+
+    def _rank_project(self, shape3, review_u_p, clear_seq=False):
+        """``ps_rtm_rank_index`` over the current review table -> the projection, a flat fp32 tensor."""
+        lib = _lib.load()
         ps, _ = self._structs()
-        shape3 = (item_ridxs.shape[0], 0 if review_u_p is None else review_u_p.shape[0], item_ridxs.shape[1])
         d, sh = self._rank_all_desc(1, 1, 1, shape3)
+        if clear_seq:
+            sh.seq_review_test = 0
         n = lib.ps_rtm_rank_index_floats(d, sh)
         if n < 0:
             raise RuntimeError("ps_rtm_rank_index_floats: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
@@ -248,10 +275,61 @@ class ProductRanker(HotPathModule):
         tab = self.review_embeddings.detach().contiguous()
         _lib.check(lib.ps_rtm_rank_index(d, sh, ps, tab.data_ptr(), _lib.ptr(review_u_p), out.data_ptr(), self._stream()),
                    'ps_rtm_rank_index')
-        idx = _CatalogueIndex()
-        idx.model, idx.index, idx.item_ridxs, idx.review_u_p, idx.shape3, idx.stamp = self, out, item_ridxs, review_u_p, shape3, stamp
-        idx.table = self.review_embeddings
-        self.__dict__['_cat_index'] = idx
+        return out
+
+    @staticmethod
+    def _timeline_check(ptr, rids, times):
+        """``timeline_index``'s check, torch ops on the tensors' own device: ``ptr`` rises from 0 to N and ``times`` never falls
+        inside an item; a RuntimeError names the first item that breaks either."""
+        N = rids.numel()
+        bad = torch.nonzero(ptr[1:] < ptr[:-1]).flatten()
+        if int(ptr[0]) != 0 or int(ptr[-1]) != N or bad.numel():
+            raise RuntimeError("timeline_index: ptr must rise from 0 to N = %d (ptr[0] = %d, ptr[-1] = %d%s)"
+                               % (N, int(ptr[0]), int(ptr[-1]), ", falls after item %d" % int(bad[0]) if bad.numel() else ""))
+        if N < 2:
+            return
+        inner = torch.ones(N - 1, dtype=torch.bool, device=ptr.device)         # a fall across two items' border is none
+        border = ptr[1:-1]
+        border = border[(border > 0) & (border < N)]
+        inner[border - 1] = False
+        at = torch.nonzero((times[1:] < times[:-1]) & inner).flatten()
+        if at.numel():
+            item = int(torch.searchsorted(ptr, at[:1] + 1, right=True)[0]) - 1
+            raise RuntimeError("timeline_index: the times of item %d are not in order (element %d of the timeline)"
+                               % (item, int(at[0]) + 1))
+
+    def timeline_index(self, ptr, rids, times, review_u_p=None):
+        """The index of ``evaluate.rank_seq_rtm``, the time-ordered evaluation (``do_seq_review_test`` without
+        ``train_review_only``): the projection of ``catalogue_index`` plus the items' time-ordered review sequences as a CSR —
+        ``ptr`` [P + 1], ``rids`` [N] review ids per item in time order, ``times`` [N] their time stamps, int64 on the device
+        (``ProdSearchDataLoader.timeline``).  A pair reads the ``iprev_review_limit`` reviews of its item that sit just before
+        ``bisect_right(times of the item, the entry's stamp)``.  Checked once, on the device: ``ptr`` starts at 0, never
+        decreases and ends at N, and ``times`` never decreases inside an item — the reference's binary search returns
+        *something* on an unsorted sequence; here that is a RuntimeError naming the item.  Works on a model built with or
+        without ``do_seq_review_test``; cached and refused when stale like a catalogue index."""
+        msg = self._rank_all_refusal(time_ordered=True)
+        if msg is not None:
+            raise NotImplementedError(msg)
+        ptr, rids, times = self._idx(ptr, 'ptr'), self._idx(rids, 'rids'), self._idx(times, 'times')
+        if ptr.dim() != 1 or ptr.numel() < 2 or rids.dim() != 1 or times.shape != rids.shape or rids.numel() < 1:
+            raise RuntimeError("timeline_index: ptr must be [P + 1], rids and times [N] with N >= 1")
+        ptr, rids, times = ptr.contiguous(), rids.contiguous(), times.contiguous()
+        review_u_p = self._rank_review_u_p(review_u_p, 'timeline_index')
+        self._rank_review_table()
+        stamp = self._rank_all_stamp(ptr, rids, times, review_u_p, self.review_embeddings)
+        cached = self.__dict__.get('_seq_index')
+        if cached is not None and cached.stamp == stamp:
+            return cached
+        self._timeline_check(ptr, rids, times)
+        P = ptr.numel() - 1
+        shape3 = (P, 0 if review_u_p is None else review_u_p.shape[0], int(self.args.iprev_review_limit))
+        # seq_review_test cleared: ps_rtm_rank_index refuses the time-ordered mode for the static rankers' sake (their [P, I]
+        # catalogue does not exist in it), but the projection holds no review list and is the same in both modes
+        out = self._rank_project(shape3, review_u_p, clear_seq=True)
+        idx = _TimelineIndex()
+        idx.model, idx.index, idx.ptr, idx.rids, idx.times = self, out, ptr, rids, times
+        idx.review_u_p, idx.shape3, idx.stamp, idx.table = review_u_p, shape3, stamp, self.review_embeddings
+        self.__dict__['_seq_index'] = idx
         return idx
 
     def forward(self, batch_data, train_pv=True, neg_word_idxs=None):

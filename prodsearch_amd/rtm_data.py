@@ -83,20 +83,22 @@ class ProdSearchRankBatch(object):
         target_prod_idxs  [B]     int64 tensor
         candi_prod_idxs   [B,C]   optional: the entry's own candidate list (``evaluate.rank_candidates_rtm``), item ids,
                                   a ragged list padded with -1
+        time_stamps       [B]     optional: the entries' time stamps in the time-ordered evaluation (``evaluate.rank_seq_rtm``)
     """
-    def __init__(self, query_idxs, user_idxs, target_prod_idxs, query_word_idxs, u_ridxs, candi_prod_idxs=None):
+    def __init__(self, query_idxs, user_idxs, target_prod_idxs, query_word_idxs, u_ridxs, candi_prod_idxs=None, time_stamps=None):
         self.query_idxs, self.user_idxs = query_idxs, user_idxs
         self.target_prod_idxs = _t(target_prod_idxs)
         self.query_word_idxs = _t(query_word_idxs)
         self.u_ridxs = _t(u_ridxs)
         self.candi_prod_idxs = _t(candi_prod_idxs)
+        self.time_stamps = _t(time_stamps)
 
     def to(self, device):
         if device == "cpu":
             return self
         mv = lambda x: None if x is None else x.to(device, non_blocking=True)
         return self.__class__(self.query_idxs, self.user_idxs, mv(self.target_prod_idxs), mv(self.query_word_idxs),
-                              mv(self.u_ridxs), mv(self.candi_prod_idxs))
+                              mv(self.u_ridxs), mv(self.candi_prod_idxs), mv(self.time_stamps))
 
 
 def make_review_words(seed, review_count, vocab_size, word_limit, word_dists=None):

@@ -338,11 +338,69 @@ class ProdSearchDataLoader(object):
         self._rank_all_check()
         ent = self.rank_entries()
         for lo in range(0, len(ent), self.batch_size):
-            lists = self.candidate_lists(range(lo, min(lo + self.batch_size, len(ent))))
-            cand = np.full((len(lists), max(1, max(len(x) for x in lists))), -1, dtype=np.int64)
-            for b, x in enumerate(lists):
-                cand[b, :len(x)] = x
-            yield self.rank_batch_from_ids(ent[lo:lo + self.batch_size], cand)
+            yield self.rank_batch_from_ids(ent[lo:lo + self.batch_size], self._padded_lists(lo, len(ent)))
+
+    def _padded_lists(self, lo, n_ent):
+        """[B, C] the candidate lists of entries ``lo ..`` of one batch, padded with -1 to the batch's widest list."""
+        lists = self.candidate_lists(range(lo, min(lo + self.batch_size, n_ent)))
+        cand = np.full((len(lists), max(1, max(len(x) for x in lists))), -1, dtype=np.int64)
+        for b, x in enumerate(lists):
+            cand[b, :len(x)] = x
+        return cand
+
+    # ------------------------------------------------------------------ the time-ordered evaluation (evaluate.rank_seq_rtm)
+    def _seq_rank_check(self):
+        if self._train:
+            raise RuntimeError("timeline / seq rank batches belong to an evaluation loader")
+        if not (self.args.do_seq_review_test and not self.args.train_review_only):
+            raise NotImplementedError("rank_seq_rtm serves do_seq_review_test without train_review_only; the static mode is "
+                                      "catalogue_reviews / rank_batches / candidate_batches")
+        if int(self.args.uprev_review_limit) < 1 or int(self.args.iprev_review_limit) < 1:
+            raise NotImplementedError("rank_seq_rtm: uprev_review_limit and iprev_review_limit must be at least 1")
+
+    def timeline(self):
+        """(``ptr`` [P + 1], ``rids`` [N], ``times`` [N]) on the device: every product's reviews in time order
+        (``global_data.i_r_seq``) with their time stamps ``review_loc_time[review, 2]`` — what the test collate bisects with
+        ``do_seq_review_test`` (prod_search_dataloader.py:73-77, 138-147) — for ``ProductRanker.timeline_index``."""
+        self._seq_rank_check()
+        c = self.corpus
+        times = np.ascontiguousarray(c.loc_time[c.i_seq, 2])
+        return tuple(self._ship(torch.from_numpy(x)) for x in (c.i_seq_ptr, c.i_seq, times))
+
+    def seq_rank_batch_from_ids(self, ids, candi_prod_idxs=None):
+        """Entries-only batch of the time-ordered evaluation: the user's reviews by ``u_r_seq[user][:loc_in_u]
+        [-uprev_review_limit:]`` (``get_user_review_idxs`` with ``do_seq``; collate.cpp:prev_reviews) and the entry's time
+        stamp ``review_loc_time[review, 2]``."""
+        self._seq_rank_check()
+        ids = np.asarray(ids, dtype=np.int64)
+        quad = self.entry_quad[ids]
+        c, lim = self.corpus, int(self.args.uprev_review_limit)
+        u_r = np.full((len(ids), lim), self.review_pad_idx, dtype=np.int64)
+        for b, (_, user, _, review) in enumerate(quad):
+            s = c.u_seq[c.u_seq_ptr[user]:c.u_seq_ptr[user + 1]]
+            s = s[:max(int(c.loc_time[review, 0]), 0)][-lim:]
+            u_r[b, :len(s)] = s
+        qw = torch.from_numpy(np.ascontiguousarray(c.query_words[quad[:, 0]]))
+        stamps = np.ascontiguousarray(c.loc_time[quad[:, 3], 2])
+        return ProdSearchRankBatch(quad[:, 0].tolist(), quad[:, 1].tolist(),
+                                   self._ship(torch.from_numpy(np.ascontiguousarray(quad[:, 2]))), self._ship(qw),
+                                   self._ship(torch.from_numpy(u_r)),
+                                   None if candi_prod_idxs is None else self._ship(torch.from_numpy(candi_prod_idxs)),
+                                   self._ship(torch.from_numpy(stamps)))
+
+    def seq_rank_batches(self):
+        """The dataset's distinct entries in the time-ordered mode, ``batch_size`` at a time."""
+        self._seq_rank_check()
+        ent = self.rank_entries()
+        for lo in range(0, len(ent), self.batch_size):
+            yield self.seq_rank_batch_from_ids(ent[lo:lo + self.batch_size])
+
+    def seq_candidate_batches(self):
+        """``seq_rank_batches`` with the entries' own candidate lists, padded with -1 as ``candidate_batches`` pads them."""
+        self._seq_rank_check()
+        ent = self.rank_entries()
+        for lo in range(0, len(ent), self.batch_size):
+            yield self.seq_rank_batch_from_ids(ent[lo:lo + self.batch_size], self._padded_lists(lo, len(ent)))
 
     # ------------------------------------------------------------------ the reference's collate_fn entry points
     def get_train_batch(self, batch):

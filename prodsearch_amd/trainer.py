@@ -11,7 +11,8 @@ validation MRR and the same TREC-style ranklist (``trainer.py:160-170``).  MI355
 * evaluation over all products (``*_candi_size < 1``) is ``evaluate.rank_all`` (one encode per row, scores and top-k
   on the device); sampled-candidate validation goes through ``model.test`` like the reference.  The review transformer
   goes through ``model.test`` over candidate chunks, or with ``args.rtm_rank_all`` through ``evaluate.rank_all_rtm``
-  (all products) / ``evaluate.rank_candidates_rtm`` (candidate lists: sampled validation, the rerank of ``test_candi_size``).
+  (all products) / ``evaluate.rank_candidates_rtm`` (candidate lists: sampled validation, the rerank of ``test_candi_size``) /
+  ``evaluate.rank_seq_rtm`` (either, in the time-ordered mode: ``do_seq_review_test`` without ``train_review_only``).
 """
 import logging
 import os
@@ -216,7 +217,31 @@ class Trainer(object):
             self.model.clear_review_embbeddings()
         return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
 
+    def _scores_rank_seq_rtm(self, args, global_data, dataset, topk, lists):
+        """``args.rtm_rank_all`` in the time-ordered mode (``do_seq_review_test`` without ``train_review_only``): one pass per
+        batch of entries over their own candidate lists (``lists``) or over all products (``evaluate.rank_seq_rtm``); returns
+        what ``_scores_rank_cand_rtm`` / ``_scores_rank_all_rtm`` return."""
+        loader = self.ExpDataloader(args, dataset, batch_size=args.valid_batch_size, shuffle=False, device=args.device)
+        tops, scores, ranks, users, queries = [], [], [], [], []
+        self.model.eval()
+        with torch.no_grad():
+            up = global_data.review_u_p if (args.use_user_emb or args.use_item_emb) else None
+            index = self.model.timeline_index(*loader.timeline(), review_u_p=up)
+            for b in (loader.seq_candidate_batches() if lists else loader.seq_rank_batches()):
+                ti, ts, rk = evaluate.rank_seq_rtm(self.model, index, b, topk)
+                tops.append(ti); scores.append(ts); ranks.append(rk.to(torch.int64) if lists else rk)
+                users += list(b.user_idxs); queries += list(b.query_idxs)
+            self.model.clear_review_embbeddings()
+        return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
+
+    @staticmethod
+    def _time_ordered(args):
+        return bool(getattr(args, 'do_seq_review_test', False)) and not args.train_review_only
+
     def validate(self, args, global_data, valid_dataset):
+        if self.rtm and getattr(args, 'rtm_rank_all', False) and self._time_ordered(args):
+            return evaluate.calc_metrics(self._scores_rank_seq_rtm(args, global_data, valid_dataset, 1,
+                                                                   args.valid_candi_size >= 1)[0], 100)
         if self.rtm and getattr(args, 'rtm_rank_all', False) and args.valid_candi_size < 1:
             return evaluate.calc_metrics(self._scores_rank_all_rtm(args, global_data, valid_dataset, 1)[0], 100)
         if self.rtm and getattr(args, 'rtm_rank_all', False):
@@ -233,7 +258,11 @@ class Trainer(object):
 
     def test(self, args, global_data, test_prod_data, rankfname="test.best_model.ranklist", cutoff=100):
         dataset = self.ExpDataset(args, global_data, test_prod_data)
-        if self.rtm and getattr(args, 'rtm_rank_all', False) and args.test_candi_size < 1:
+        if self.rtm and getattr(args, 'rtm_rank_all', False) and self._time_ordered(args):
+            lists = args.test_candi_size >= 1
+            rank, top_idx, top_score, users, queries = self._scores_rank_seq_rtm(
+                args, global_data, dataset, min(cutoff, args.test_candi_size if lists else global_data.product_size, 256), lists)
+        elif self.rtm and getattr(args, 'rtm_rank_all', False) and args.test_candi_size < 1:
             rank, top_idx, top_score, users, queries = self._scores_rank_all_rtm(
                 args, global_data, dataset, min(cutoff, global_data.product_size, 256))
         elif self.rtm and getattr(args, 'rtm_rank_all', False):
