@@ -12,18 +12,18 @@ extern "C" {
  * the rerank of --test_candi_size / uq_pids lists (trainer.py:189-226) — which nothing in it forbids: it never depended on which
  * items are scored.  desc, shape, params, index, item_ridxs: those of ps_rtm_rank_all, the same catalogue index; candi_prod_idxs
  * [B, C] int64 item ids, a slot outside [0, P) (the -1 padding of a ragged list) is dead: scored -inf, never ranked or listed.
- * Two entries' lists share no item, so rr_cand_kernel reads the K / V rows by review id from the index, one wave per pair, and
+ * Two entries' lists share no item, so rr_slot_kernel reads the K / V rows by review id from the index, one wave per pair, and
  * holds no LDS tile.  Refusals: those of ps_rtm_rank_all, with its messages; C >= 1; B * cands_per_pass < 2^30. */
 /* bytes of scratch with `cands_per_pass` columns of the lists scored per pass (<= 0: the default, 32768 pairs); -1: refused /
  * bad sizes.  ps_rtm_rank_candidates sizes its passes from the scratch it is given: the most columns that fit. */
 int64_t ps_rtm_rank_cand_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk,
                                        int64_t cands_per_pass);
-/* What ps_rtm_rank_candidates launches, from the rules the launcher itself reads (csrc/rtm_rank.hip: rr_cand_pass_layout, rr_epl,
+/* What ps_rtm_rank_candidates launches, from the rules the launcher itself reads (csrc/rtm_rank.hip: rr_pass_layout, rr_epl,
  * rr_lph, rr_tail_fused, rr_query_fs_fused).  Host only: no HIP call. */
 typedef struct PsRtmRankCandPlan {
   int64_t cands_per_pass;       /* columns of the lists scored per pass: the most whose pairs fit the scratch          */
   int64_t passes;               /* ceil(C / cands_per_pass); a ragged last pass runs at the full pass shape            */
-  int32_t epl;                  /* d / 64: the instantiation of rr_entry_kernel / rr_cand_kernel                       */
+  int32_t epl;                  /* d / 64: the instantiation of rr_entry_kernel / rr_slot_kernel                       */
   int32_t lph;                  /* 64 / H: lanes per head                                                              */
   int32_t tail_fused;           /* the per-pair tail is the fused d = 128 kernel                                       */
   int32_t query_fs_fused;       /* the fs query encoder's projection runs inside the embed launch                      */

@@ -13,8 +13,8 @@ extern "C" {
  * item's review list depends on the entry (prod_search_dataloader.py:60-77, 138-147; prod_search_dataset.py:133-151).  A pair
  * (entry e, item i) reads the shape->I (iprev_review_limit) reviews of item i that sit just before a cut in the item's
  * time-ordered sequence, cut = the number of its times <= time_stamps[e] (bisect_right).  The key / value rows still depend on
- * the review id alone, so the projection and the entry side are ps_rtm_rank_all's; rr_seq_kernel puts a wave-wide search and a
- * window lookup in front of rr_cand_kernel's walk.  A pair's bits equal those ps_rtm_rank_all / ps_rtm_rank_candidates give
+ * the review id alone, so the projection and the entry side are ps_rtm_rank_all's; rr_slot_kernel puts a wave-wide search and a
+ * window lookup in front of the same walk.   A pair's bits equal those ps_rtm_rank_all / ps_rtm_rank_candidates give
  * the same list in a static catalogue.
  * The entries accept either value of shape->seq_review_test: the field says what the run is, and these entries serve both.
  * Refusals: the others of ps_rtm_rank_all, with its messages; C >= 1 with a list; B * slots_per_pass < 2^30; a null timeline. */
@@ -32,12 +32,12 @@ typedef struct PsRtmSeqTimeline {   /* device pointers */
  * ps_rtm_rank_seq sizes its passes from the scratch it is given: the most columns that fit. */
 int64_t ps_rtm_rank_seq_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk,
                                       int64_t slots_per_pass);
-/* What ps_rtm_rank_seq launches, from the rules the launcher itself reads (csrc/rtm_rank.hip: rr_seq_pass_layout, rr_epl, rr_lph,
+/* What ps_rtm_rank_seq launches, from the rules the launcher itself reads (csrc/rtm_rank.hip: rr_pass_layout, rr_epl, rr_lph,    
  * rr_tail_fused, rr_query_fs_fused).  Host only: no HIP call. */
 typedef struct PsRtmRankSeqPlan {
   int64_t slots_per_pass;       /* columns scored per pass: the most whose pairs fit the scratch                         */
   int64_t passes;               /* ceil(columns / slots_per_pass); a ragged last pass runs at the full pass shape        */
-  int32_t epl;                  /* d / 64: the instantiation of rr_entry_kernel / rr_seq_kernel                          */
+  int32_t epl;                  /* d / 64: the instantiation of rr_entry_kernel / rr_slot_kernel                         */
   int32_t lph;                  /* 64 / H: lanes per head                                                                */
   int32_t tail_fused;           /* the per-pair tail is the fused d = 128 kernel                                         */
   int32_t query_fs_fused;       /* the fs query encoder's projection runs inside the embed launch                        */

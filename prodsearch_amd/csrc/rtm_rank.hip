@@ -18,13 +18,16 @@
 //   rr_head                wo . enc + b into the dense score matrix; the selection is rank.hip's (rank.h)
 // The same pass over per-entry CANDIDATE LISTS (include/prodsearch_rtm_cand.h, ps_rtm_rank_cand_* /
 // ps_rtm_rank_candidates: sampled validation, the rerank of test_candi_size lists) shares the index and the entry side:
-//   rr_cand                per (entry, slot of its list): one wave per pair, the K / V rows straight from KR / VR — no LDS tile,
-//                          two entries' lists have no item in common; the same rr_step in the same order as rr_pair
-//   rr_cand_head / _target / _ids   scores [B, C] (-inf at dead slots), the target's column, the selected columns -> item ids
+//   rr_slot<EPL, false>    per (entry, slot of its list): one wave per pair, the K / V rows straight from KR / VR — no LDS tile,
+//                          two entries' lists have no item in common
+//   rr_head / rr_cand_target / _ids   scores [B, C] (-inf at dead slots), the target's column, the selected columns -> item ids
 // The TIME-ORDERED evaluation (include/prodsearch_rtm_seq.h, ps_rtm_rank_seq*: do_seq_review_test without
 // train_review_only) keeps the index and the entry side too; what changes is which review ids a pair reads:
-//   rr_seq                 per (entry, slot): the item's time-ordered sequence is searched wave-wide for the entry's time stamp and the
-//                          iprev_review_limit reviews just before the cut are the pair's list; the walk after that is rr_cand's
+//   rr_slot<EPL, true>     per (entry, slot): the item's time-ordered sequence is searched wave-wide for the entry's time stamp and the
+//                          iprev_review_limit reviews just before the cut are the pair's list
+// Every key / value walk is rr_walk — the one call of rr_step — over a row source (review ids held one per lane, or a
+// workgroup's LDS tile), and the three launch entries are one driver (rr_run) over one column description (RrCols): a further
+// column source adds a row source or a slot rule and nothing else.
 // fp32 throughout, plain C++; the per-pair tail is the encoder's own (enc_tail_forward).
 #include "rtm.h"
 #include "../../include/prodsearch_rtm_cand.h"
@@ -33,6 +36,7 @@
 #include "wgrad.h"      // gp / run1
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 
 #define RR_IT_MAX 16                 // items of one workgroup's tile
 #define RR_LDS_MAX (128 * 1024)      // bytes of K / V rows a workgroup may hold
@@ -78,20 +82,43 @@ static RrIndex rr_index_layout(const PsRtmDesc& D) {
 struct RrWs {
   Ws w;                       // the tail's slice, laid out for enc_tail_forward: n_in = B, fan = tile, S = 1, qpos = 0
   int64_t qmean, qemb, x0, qp, k0, v0, em, es, eacc, entn, S, sel, total;
-  int64_t tcol;               // candidate lists only: the target's column per entry (int64)
+  int64_t tcol;               // RrCols::tcol: the target's column per entry (int64)
   int64_t ldS, sel_bytes;
   int tile;
   bool fuse;
 };
 static bool rr_tail_fused(const PsRtmDesc& D) { return ps_fusion_enabled() && mlp_fused_serves(D.d, D.F); }
-// `cols` scored columns per entry (the catalogue's items, or the slots of a candidate list), `tile` of them per pass
-static int rr_layout_cols(const PsRtmDesc& D, int64_t cols, int topk, int64_t tile, const char* what, RrWs& r) {
+// The scored columns of a call: the catalogue's items, or the slots of the entries' candidate lists.  One description serves the
+// layout, the pass size, the plans and the driver; `name` / `unit` word the messages of the entry it was made for.
+struct RrCols {
+  int64_t n;                  // columns per entry
+  bool list;                  // they are the slots of per-entry lists: dead slots, the selection over columns -> item ids
+  bool tcol;                  // the scratch ends with the target's column per entry (int64)
+  const char *name, *unit;
+};
+static RrCols rr_all_cols(const PsRtmRankShape& S) { return RrCols{S.n_items, false, false, "rtm rank_all", "item"}; }
+static int rr_cand_cols(int64_t C, RrCols& c) {
+  PS_REQUIRE(C >= 1 && C < ((int64_t)1 << 31), "rtm rank_candidates: %lld candidates per entry (at least 1)", (long long)C);
+  c = RrCols{C, true, true, "rtm rank_candidates", "candidate"};
+  return PS_OK;
+}
+// the time-ordered entries: the slots of the lists (C of them) or, with no list, the P catalogue rows
+static int rr_seq_cols(const PsRtmRankShape& S, int64_t C, bool list, RrCols& c) {
+  const int64_t cols = list ? C : S.n_items;
+  PS_REQUIRE(!list || cols >= 1, "rtm rank_seq: %lld candidates per entry (at least 1)", (long long)cols);
+  PS_REQUIRE(cols >= 1 && cols < ((int64_t)1 << 31), "rtm rank_seq: %lld columns", (long long)cols);
+  c = RrCols{cols, list, true, "rtm rank_seq", "slot"};
+  return PS_OK;
+}
+// `tile` of the columns per pass
+static int rr_layout(const PsRtmDesc& D, const RrCols& c, int topk, int64_t tile, RrWs& r) {
+  PS_REQUIRE(tile >= 1 && tile <= c.n && (int64_t)D.B * tile < ((int64_t)1 << 30), "%s: %lld %ss per pass", c.name, (long long)tile, c.unit);
   memset(&r, 0, sizeof(r));
-  const int64_t B = D.B, d = D.d, F = D.F, P = cols;
+  const int64_t B = D.B, d = D.d, F = D.F, P = c.n;
   r.tile = (int)tile;
   r.fuse = rr_tail_fused(D);
   r.sel_bytes = rank_select_scratch_bytes((int)B, P, topk);
-  PS_REQUIRE(r.sel_bytes >= 0, "%s: topk must be 1..256", what);
+  PS_REQUIRE(r.sel_bytes >= 0, "%s: topk must be 1..256", c.name);
   int64_t cur = 0;
   r.qmean = rtake(cur, B * d); r.qemb = rtake(cur, B * d); r.x0 = rtake(cur, B * d);
   r.qp = rtake(cur, B * d); r.k0 = rtake(cur, B * d); r.v0 = rtake(cur, B * d);
@@ -110,21 +137,7 @@ static int rr_layout_cols(const PsRtmDesc& D, int64_t cols, int topk, int64_t ti
   w.Mf = (int)M;
   w.fin_stats = rtake(cur, M * 2); w.enc = rtake(cur, M * d);
   w.total = cur;
-  r.total = cur;
-  return PS_OK;
-}
-static int rr_layout(const PsRtmDesc& D, const PsRtmRankShape& Sh, int topk, int64_t tile, RrWs& r) {
-  const int64_t P = Sh.n_items;
-  PS_REQUIRE(tile >= 1 && tile <= P && (int64_t)D.B * tile < ((int64_t)1 << 30), "rtm rank_all: %lld items per pass", (long long)tile);
-  return rr_layout_cols(D, P, topk, tile, "rtm rank_all", r);
-}
-// a candidate list of C slots per entry, `tile` columns of it per pass: the same slices, plus the target's column
-static int rr_cand_layout(const PsRtmDesc& D, int64_t C, int topk, int64_t tile, RrWs& r) {
-  PS_REQUIRE(C >= 1 && C < ((int64_t)1 << 31), "rtm rank_candidates: %lld candidates per entry (at least 1)", (long long)C);
-  PS_REQUIRE(tile >= 1 && tile <= C && (int64_t)D.B * tile < ((int64_t)1 << 30), "rtm rank_candidates: %lld candidates per pass", (long long)tile);
-  TRY(rr_layout_cols(D, C, topk, tile, "rtm rank_candidates", r));
-  int64_t cur = r.total;
-  r.tcol = rtake(cur, 2 * (int64_t)D.B);
+  if (c.tcol) r.tcol = rtake(cur, 2 * (int64_t)B);
   r.total = cur;
   return PS_OK;
 }
@@ -138,8 +151,8 @@ struct RrK {
   const float *qp, *k0, *v0;
   float *em, *es, *eacc; int32_t* entn;
   float* ctx;
-  const int64_t* candi; int C;         // rr_cand_kernel: the lists [B, C]; i0 is then the pass's first column
-  const int64_t *tl_ptr, *tl_rids, *tl_times, *stamps; int64_t tl_n;   // rr_seq_kernel: the timeline (CSR + times) and the entries' stamps [B]
+  const int64_t* candi; int C;         // rr_slot_kernel: the lists [B, C] (or null); i0 is the pass's first column
+  const int64_t *tl_ptr, *tl_rids, *tl_times, *stamps; int64_t tl_n;   // rr_slot_kernel<EPL, true>: the timeline (CSR + times) and the entries' stamps [B]
 };
 
 // T[r] = rev[r] (+ user_emb[author]) (+ product_emb[item]) with the id rule of rtm_embed_kernel: an id outside [0, pad] adds nothing
@@ -224,6 +237,55 @@ __device__ __forceinline__ int rr_leading(int id, int pad) {
   return inv ? __builtin_ctzll(inv) : 64;
 }
 
+// Where a walk's rows come from: two fixed bases and ONE offset per row, K[off(jj) + column] / V[off(jj) + column].  (Handing
+// back a K and a V pointer per row instead costs the slot kernel six VGPRs and a wave of occupancy at d = 128.)
+struct RrIdRows {                                    // by review id, held one per lane: rows of KR / VR
+  const float *K, *V; int id, d;
+  __device__ __forceinline__ size_t off(int jj) const { return (size_t)__shfl(id, jj, 64) * d; }
+};
+struct RrLdsRows {                                   // a workgroup's LDS tile [I][2][d]: K = the item's rows, V = K + d
+  const float *K, *V; int d;
+  __device__ __forceinline__ size_t off(int jj) const { return (size_t)(2 * jj) * d; }
+};
+// THE key / value walk: rows 0 .. n - 1 of `rows`, at positions pos0 .. of the [position] tables kt / vt, join the running softmax
+// (m, s, acc) in groups of RR_U, the 2 * RR_U row loads of a group issued together.  Every kernel walks through here, so two of
+// them that see the same rows give the same bits.
+template <int EPL, class Rows>
+__device__ __forceinline__ void rr_walk(const Rows rows, int n, int pos0, const float* kt, const float* vt, int d, size_t col, int lph,
+                                        const float (&q)[EPL], float& m, float& s, float (&acc)[EPL]) {
+  float k[RR_U][EPL], v[RR_U][EPL];
+  for (int j = 0; j < n; j += RR_U) {
+#pragma unroll
+    for (int u = 0; u < RR_U; ++u) {
+      const int jj = j + u < n ? j + u : n - 1;     // (a slot past the list repeats its last row; rr_step drops it)
+      const size_t off = rows.off(jj) + col;
+      const size_t pos = (size_t)(pos0 + jj) * d + col;
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) {
+        k[u][i] = rows.K[off + i] + kt[pos + i];
+        v[u][i] = rows.V[off + i] + vt[pos + i];
+      }
+    }
+    rr_step<EPL>(q, k, v, n - j, lph, m, s, acc);
+  }
+}
+// the pair side of a walk: entry e's state over {query, the user's reviews} continues over `n` rows of an item at positions
+// 1 + n_u .. (segment 2), and the normalised context row goes to `out`
+template <int EPL, class Rows>
+__device__ __forceinline__ void rr_pair_walk(const RrK& a, int e, const Rows rows, int n, int lane, float* out) {
+  const int d = a.d, nu = a.entn[e];
+  n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;        // the sequence never exceeds 1 + total_review_limit positions
+  const size_t col = (size_t)lane * EPL;
+  float q[EPL], acc[EPL];
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) { q[i] = a.qp[(size_t)e * d + col + i]; acc[i] = a.eacc[(size_t)e * d + col + i]; }
+  float m = a.em[(size_t)e * 64 + lane], s = a.es[(size_t)e * 64 + lane];
+  rr_walk<EPL>(rows, n, 1 + nu, a.kt + (size_t)a.T1 * d, a.vt + (size_t)a.T1 * d, d, col, a.lph, q, m, s, acc);
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) out[col + i] = acc[i] * inv;
+}
+
 // once per entry: the softmax state over {query token, the user's reviews at positions 1 .. n_u, segment 1}
 template <int EPL>
 __global__ __launch_bounds__(256) void rr_entry_kernel(const RrK a) {
@@ -234,7 +296,7 @@ __global__ __launch_bounds__(256) void rr_entry_kernel(const RrK a) {
   const int id = lane < a.U ? (int)rclamp(a.u_r[(size_t)e * a.U + lane], a.RC - 1) : pad;
   int nu = rr_leading(id, pad);
   nu = nu < a.T1 - 1 ? nu : a.T1 - 1;
-  float q[EPL], k[RR_U][EPL], v[RR_U][EPL], acc[EPL];
+  float q[EPL], acc[EPL];
   const size_t col = (size_t)lane * EPL;
   float m = 0.f, s = 1.f;                          // the query token's own key opens the state: weight exp(0) = 1 on v0
 #pragma unroll
@@ -243,19 +305,7 @@ __global__ __launch_bounds__(256) void rr_entry_kernel(const RrK a) {
     m = __builtin_fmaf(q[i], a.k0[(size_t)e * d + col + i], m);
   }
   m = group_sum(m, a.lph);
-  for (int j = 0; j < nu; j += RR_U) {
-#pragma unroll
-    for (int u = 0; u < RR_U; ++u) {
-      const int jj = j + u < nu ? j + u : nu - 1;   // (a slot past the list repeats its last row; rr_step drops it)
-      const size_t r = (size_t)__shfl(id, jj, 64);
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) {
-        k[u][i] = a.KR[r * d + col + i] + a.kt[(size_t)(1 + jj) * d + col + i];
-        v[u][i] = a.VR[r * d + col + i] + a.vt[(size_t)(1 + jj) * d + col + i];
-      }
-    }
-    rr_step<EPL>(q, k, v, nu - j, a.lph, m, s, acc);
-  }
+  rr_walk<EPL>(RrIdRows{a.KR, a.VR, id, d}, nu, 1, a.kt, a.vt, d, col, a.lph, q, m, s, acc);
   a.em[(size_t)e * 64 + lane] = m; a.es[(size_t)e * 64 + lane] = s;
 #pragma unroll
   for (int i = 0; i < EPL; ++i) a.eacc[(size_t)e * d + col + i] = acc[i];
@@ -299,105 +349,36 @@ __global__ __launch_bounds__(256) void rr_pair_kernel(const RrK a) {
     }
   }
   __syncthreads();
-  const size_t col = (size_t)lane * EPL;
-  const float* kt2 = a.kt + (size_t)a.T1 * d;
-  const float* vt2 = a.vt + (size_t)a.T1 * d;
   for (int p = wv; p < a.B * a.IT; p += 4) {
     const int e = p / a.IT, it = p - e * a.IT;
     if (t0 + it >= a.tile) continue;                // (wave-uniform)
-    const int nu = a.entn[e];
-    int n = s_n[it];
-    n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;      // the sequence never exceeds 1 + total_review_limit positions
-    float q[EPL], k[RR_U][EPL], v[RR_U][EPL], acc[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) { q[i] = a.qp[(size_t)e * d + col + i]; acc[i] = a.eacc[(size_t)e * d + col + i]; }
-    float m = a.em[(size_t)e * 64 + lane], s = a.es[(size_t)e * 64 + lane];
     const float* src = kv + (size_t)it * a.I * 2 * d;
-    for (int j = 0; j < n; j += RR_U) {
-#pragma unroll
-      for (int u = 0; u < RR_U; ++u) {
-        const int jj = j + u < n ? j + u : n - 1;   // (a slot past the list repeats its last row; rr_step drops it)
-        const size_t pos = (size_t)(1 + nu + jj) * d + col;
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) {
-          k[u][i] = src[(size_t)(2 * jj) * d + col + i] + kt2[pos + i];
-          v[u][i] = src[(size_t)(2 * jj + 1) * d + col + i] + vt2[pos + i];
-        }
-      }
-      rr_step<EPL>(q, k, v, n - j, a.lph, m, s, acc);
-    }
-    const float inv = 1.f / s;
-    float* out = a.ctx + ((size_t)e * a.tile + t0 + it) * d + col;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) out[i] = acc[i] * inv;
+    rr_pair_walk<EPL>(a, e, RrLdsRows{src, src + d, d}, s_n[it], lane, a.ctx + ((size_t)e * a.tile + t0 + it) * d);
   }
 }
 
-// per (entry, slot of the entry's own candidate list): one wave per pair.  Two entries' lists have no item in common, so an LDS
-// tile would amortise nothing: the K / V rows come by review id straight from KR / VR, as in rr_entry_kernel, the 2 * RR_U row
-// loads of a group issued together.  Slot t of the pass is column min(i0 + t, C - 1) (a ragged last pass runs at the full pass
-// shape); a dead slot (id outside [0, P)) is computed on item 0 — every load stays unconditional — and rr_cand_head_kernel writes
-// its score as -inf.  The walk is rr_pair_kernel's: the same rr_step on the same operands in the same groups, hence the same bits.
-template <int EPL>
-__global__ __launch_bounds__(256) void rr_cand_kernel(const RrK a) {
+// per (entry, slot): one wave per pair.  The slot's item is the entry's own list's (candi: slot t of the pass is column
+// min(i0 + t, C - 1), a dead slot — an id outside [0, P) — is computed on item 0 and rr_head_kernel writes its score as -inf), or
+// without a list catalogue row min(i0 + t, P - 1); either way a ragged last pass runs at the full pass shape and every load stays
+// unconditional.  Two entries' lists have no item in common, so an LDS tile would amortise nothing: the K / V rows come by review
+// id straight from KR / VR, as in rr_entry_kernel.
+//   SEQ = false: the pair's list is the item's static [P, I] row; always launched with lists.
+//   SEQ = true:  the time-ordered evaluation (do_seq_review_test without train_review_only, prod_search_dataloader.py:60-77,
+// 138-147): the list is the I reviews of the item just before a cut in the item's time-ordered sequence, cut = bisect_right(times
+// of the sequence, the entry's stamp).  The search is wave-wide: each round the 64 lanes probe 64 evenly spaced elements of the
+// open range, one ballot of time <= stamp and its population count leave the stretch between two probes: one round up to 64
+// reviews, two up to 4,160, three up to 266,304.  Every load of the search and of the window is unconditional on an index clamped
+// into [0, N - 1] (N >= 1); what a lane may use of it is decided afterwards.
+// From the list on both are rr_pair_walk, so a pair's bits are those of rr_pair_kernel on the same list.
+template <int EPL, bool SEQ>
+__global__ __launch_bounds__(256) void rr_slot_kernel(const RrK a) {
   const int lane = threadIdx.x & 63;
   const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   if (p >= a.B * a.tile) return;                    // (wave-uniform)
   const int e = p / a.tile, t = p - e * a.tile;
-  const int d = a.d, pad = (int)(a.RC - 1);
-  int c = a.i0 + t;
-  c = c < a.C ? c : a.C - 1;
-  int64_t gi = a.candi[(size_t)e * a.C + c];
-  gi = (gi < 0 || gi >= a.P) ? 0 : gi;
-  const int id = lane < a.I ? (int)rclamp(a.item_r[(size_t)gi * a.I + lane], a.RC - 1) : pad;
-  const int nu = a.entn[e];
-  int n = rr_leading(id, pad);
-  n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;        // the sequence never exceeds 1 + total_review_limit positions
-  const size_t col = (size_t)lane * EPL;
-  const float* kt2 = a.kt + (size_t)a.T1 * d;
-  const float* vt2 = a.vt + (size_t)a.T1 * d;
-  float q[EPL], k[RR_U][EPL], v[RR_U][EPL], acc[EPL];
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) { q[i] = a.qp[(size_t)e * d + col + i]; acc[i] = a.eacc[(size_t)e * d + col + i]; }
-  float m = a.em[(size_t)e * 64 + lane], s = a.es[(size_t)e * 64 + lane];
-  for (int j = 0; j < n; j += RR_U) {
-#pragma unroll
-    for (int u = 0; u < RR_U; ++u) {
-      const int jj = j + u < n ? j + u : n - 1;     // (a slot past the list repeats its last row; rr_step drops it)
-      const size_t r = (size_t)__shfl(id, jj, 64);
-      const size_t pos = (size_t)(1 + nu + jj) * d + col;
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) {
-        k[u][i] = a.KR[r * d + col + i] + kt2[pos + i];
-        v[u][i] = a.VR[r * d + col + i] + vt2[pos + i];
-      }
-    }
-    rr_step<EPL>(q, k, v, n - j, a.lph, m, s, acc);
-  }
-  const float inv = 1.f / s;
-  float* out = a.ctx + ((size_t)e * a.tile + t) * d + col;
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) out[i] = acc[i] * inv;
-}
-
-// per (entry, slot) in the time-ordered evaluation (do_seq_review_test without train_review_only, prod_search_dataloader.py:60-77,
-// 138-147): the pair's list is not a fixed [P, I] row but the I reviews of the item just before a cut in the item's time-ordered
-// sequence, cut = bisect_right(times of the sequence, the entry's stamp).  One wave per pair as rr_cand_kernel; with a list (candi)
-// the item is the slot's, a dead slot computed on item 0; without one it is catalogue row min(i0 + t, P - 1).
-// The search is wave-wide: each round the 64 lanes probe 64 evenly spaced elements of the open range, one ballot of time <= stamp and
-// its population count leave the stretch between two probes: one round up to 64 reviews, two up to 4,160, three up to 266,304.
-// Every load of the search and of the window is unconditional on an index clamped into [0, N - 1] (N >= 1); what a lane may use of
-// it is decided afterwards.  From the window on the code is rr_cand_kernel's: the same rr_step on the same operands in the same
-// groups, so a pair's bits are those of the static kernels on the same list.
-template <int EPL>
-__global__ __launch_bounds__(256) void rr_seq_kernel(const RrK a) {
-  const int lane = threadIdx.x & 63;
-  const int p = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-  if (p >= a.B * a.tile) return;                    // (wave-uniform)
-  const int e = p / a.tile, t = p - e * a.tile;
-  const int d = a.d, pad = (int)(a.RC - 1);
+  const int pad = (int)(a.RC - 1);
   int64_t gi;
-  if (a.candi) {                                    // (wave-uniform)
+  if (!SEQ || a.candi) {                            // (wave-uniform; the static rows without a list are rr_pair_kernel's)
     int c = a.i0 + t;
     c = c < a.C ? c : a.C - 1;
     gi = a.candi[(size_t)e * a.C + c];
@@ -406,63 +387,42 @@ __global__ __launch_bounds__(256) void rr_seq_kernel(const RrK a) {
     gi = a.i0 + t;
     gi = gi < a.P ? gi : a.P - 1;
   }
-  const int64_t stamp = a.stamps[e], last = a.tl_n - 1;
-  int64_t lo = a.tl_ptr[gi], hi = a.tl_ptr[gi + 1];
-  lo = lo < 0 ? 0 : (lo > a.tl_n ? a.tl_n : lo);    // (a corrupt ptr cannot send a load outside the arrays)
-  hi = hi < lo ? lo : (hi > a.tl_n ? a.tl_n : hi);
-  // the cut lies in [b0, b1]: every element before b0 is <= stamp, every element from b1 on is greater
-  int64_t b0 = lo, b1 = hi;
-  while (b1 > b0) {                                 // (wave-uniform: b0 / b1 come from ballots)
-    const int64_t len = b1 - b0, step = (len + 63) >> 6;
-    const int64_t off = (int64_t)lane * step;
-    int64_t ix = b0 + off;
-    ix = ix < last ? ix : last;
-    const bool le = a.tl_times[ix] <= stamp && off < len;
-    const int c = __popcll(__ballot(le));            // the probes are in time order: the first c of them hold
-    if (c == 0) { b1 = b0; break; }
-    const int64_t nb1 = b0 + (int64_t)c * step;
-    b0 = b0 + (int64_t)(c - 1) * step + 1;
-    b1 = nb1 < b1 ? nb1 : b1;
-  }
-  const int64_t cut = b0 - lo;
-  const int nraw = (int)(cut < a.I ? cut : a.I);
-  int64_t wx = b0 - nraw + lane;
-  wx = wx < 0 ? 0 : (wx < last ? wx : last);
-  const int rid = (int)rclamp(a.tl_rids[wx], a.RC - 1);
-  const int id = lane < nraw ? rid : pad;
-  const int nu = a.entn[e];
-  int n = rr_leading(id, pad);
-  n = n < a.T1 - 1 - nu ? n : a.T1 - 1 - nu;        // the sequence never exceeds 1 + total_review_limit positions
-  const size_t col = (size_t)lane * EPL;
-  const float* kt2 = a.kt + (size_t)a.T1 * d;
-  const float* vt2 = a.vt + (size_t)a.T1 * d;
-  float q[EPL], k[RR_U][EPL], v[RR_U][EPL], acc[EPL];
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) { q[i] = a.qp[(size_t)e * d + col + i]; acc[i] = a.eacc[(size_t)e * d + col + i]; }
-  float m = a.em[(size_t)e * 64 + lane], s = a.es[(size_t)e * 64 + lane];
-  for (int j = 0; j < n; j += RR_U) {
-#pragma unroll
-    for (int u = 0; u < RR_U; ++u) {
-      const int jj = j + u < n ? j + u : n - 1;     // (a slot past the list repeats its last row; rr_step drops it)
-      const size_t r = (size_t)__shfl(id, jj, 64);
-      const size_t pos = (size_t)(1 + nu + jj) * d + col;
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) {
-        k[u][i] = a.KR[r * d + col + i] + kt2[pos + i];
-        v[u][i] = a.VR[r * d + col + i] + vt2[pos + i];
-      }
+  int id;
+  if constexpr (SEQ) {
+    const int64_t stamp = a.stamps[e], last = a.tl_n - 1;
+    int64_t lo = a.tl_ptr[gi], hi = a.tl_ptr[gi + 1];
+    lo = lo < 0 ? 0 : (lo > a.tl_n ? a.tl_n : lo);  // (a corrupt ptr cannot send a load outside the arrays)
+    hi = hi < lo ? lo : (hi > a.tl_n ? a.tl_n : hi);
+    // the cut lies in [b0, b1]: every element before b0 is <= stamp, every element from b1 on is greater
+    int64_t b0 = lo, b1 = hi;
+    while (b1 > b0) {                               // (wave-uniform: b0 / b1 come from ballots)
+      const int64_t len = b1 - b0, step = (len + 63) >> 6;
+      const int64_t off = (int64_t)lane * step;
+      int64_t ix = b0 + off;
+      ix = ix < last ? ix : last;
+      const bool le = a.tl_times[ix] <= stamp && off < len;
+      const int c = __popcll(__ballot(le));          // the probes are in time order: the first c of them hold
+      if (c == 0) { b1 = b0; break; }
+      const int64_t nb1 = b0 + (int64_t)c * step;
+      b0 = b0 + (int64_t)(c - 1) * step + 1;
+      b1 = nb1 < b1 ? nb1 : b1;
     }
-    rr_step<EPL>(q, k, v, n - j, a.lph, m, s, acc);
+    const int64_t cut = b0 - lo;
+    const int nraw = (int)(cut < a.I ? cut : a.I);
+    int64_t wx = b0 - nraw + lane;
+    wx = wx < 0 ? 0 : (wx < last ? wx : last);
+    const int rid = (int)rclamp(a.tl_rids[wx], a.RC - 1);
+    id = lane < nraw ? rid : pad;
+  } else {
+    id = lane < a.I ? (int)rclamp(a.item_r[(size_t)gi * a.I + lane], a.RC - 1) : pad;
   }
-  const float inv = 1.f / s;
-  float* out = a.ctx + ((size_t)e * a.tile + t) * d + col;
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) out[i] = acc[i] * inv;
+  rr_pair_walk<EPL>(a, e, RrIdRows{a.KR, a.VR, id, a.d}, rr_leading(id, pad), lane, a.ctx + ((size_t)e * a.tile + t) * a.d);
 }
 
-// S[e][c0 + t] = wo . enc[e * tile + t] + b as rr_head_kernel, -inf for a dead slot
-__global__ __launch_bounds__(256) void rr_cand_head_kernel(const float* enc, const float* wo_w, const float* wo_b, const int64_t* candi,
-                                                           int B, int tile, int nv, int d, int c0, int C, int P, int ldS, float* S) {
+// S[e][c0 + t] = wo . enc[e * tile + t] + b  (rtm_score_kernel's sum order), one wave per pair; with the entries' lists (candi, may
+// be null) -inf for a dead slot
+__global__ __launch_bounds__(256) void rr_head_kernel(const float* enc, const float* wo_w, const float* wo_b, const int64_t* candi,
+                                                      int B, int tile, int nv, int d, int c0, int C, int P, int ldS, float* S) {
   const int lane = threadIdx.x & 63;
   const int n = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   if (n >= B * tile) return;
@@ -471,8 +431,11 @@ __global__ __launch_bounds__(256) void rr_cand_head_kernel(const float* enc, con
   float s = 0.f;
   for (int c = lane; c < d; c += 64) s += enc[(size_t)n * d + c] * wo_w[c];
   s = wave_sum(s) + wo_b[0];
-  const int64_t gi = candi[(size_t)e * C + c0 + t];
-  if (lane == 0) S[(size_t)e * ldS + c0 + t] = (gi < 0 || gi >= P) ? -INFINITY : s;
+  if (candi) {                                      // (uniform)
+    const int64_t gi = candi[(size_t)e * C + c0 + t];
+    s = (gi < 0 || gi >= P) ? -INFINITY : s;
+  }
+  if (lane == 0) S[(size_t)e * ldS + c0 + t] = s;
 }
 // the first live column of every entry's list that holds its target; C (not a column: rank 0) where there is none.  One wave per entry.
 __global__ __launch_bounds__(256) void rr_cand_target_kernel(const int64_t* candi, const int64_t* target, int B, int C, int P, int64_t* tcol) {
@@ -497,20 +460,6 @@ __global__ __launch_bounds__(256) void rr_cand_ids_kernel(const int64_t* candi, 
   const int e = n / topk;
   const int64_t c = top_idx[n];
   top_idx[n] = (c < 0 || c >= C || top_score[n] == -INFINITY) ? -1 : candi[(size_t)e * C + c];
-}
-
-// scores[e][i0 + t] = wo . enc[e * tile + t] + b  (rtm_score_kernel's sum order), one wave per pair
-__global__ __launch_bounds__(256) void rr_head_kernel(const float* enc, const float* wo_w, const float* wo_b, int B, int tile, int nv, int d,
-                                                      int i0, int ldS, float* S) {
-  const int lane = threadIdx.x & 63;
-  const int n = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-  if (n >= B * tile) return;
-  const int e = n / tile, t = n - e * tile;
-  if (t >= nv) return;
-  float s = 0.f;
-  for (int c = lane; c < d; c += 64) s += enc[(size_t)n * d + c] * wo_w[c];
-  s = wave_sum(s) + wo_b[0];
-  if (lane == 0) S[(size_t)e * ldS + i0 + t] = s;
 }
 
 // ------------------------------------------------------------------ host side
@@ -577,23 +526,20 @@ extern "C" int ps_rtm_rank_index(const PsRtmDesc* desc, const PsRtmRankShape* sh
   return run1(pv, st);
 }
 
-static int64_t rr_default_tile(const PsRtmDesc& D, const PsRtmRankShape& S) {
+// ---- what a call launches: the launch entries and the plans read the same rules
+static int64_t rr_default_tile(const PsRtmDesc& D, int64_t cols) {
   int64_t t = RR_PASS_PAIRS / D.B;
   t = t < 1 ? 1 : t;
-  return t < S.n_items ? t : S.n_items;
+  return t < cols ? t : cols;
 }
-
-extern "C" int64_t ps_rtm_rank_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t items_per_pass) {
-  if (!desc || !shape) { ps_set_error("rtm rank scratch: null argument"); return -1; }
-  if (rr_check(*desc, *shape)) return -1;
-  int64_t tile = items_per_pass > 0 ? items_per_pass : rr_default_tile(*desc, *shape);
-  if (tile > shape->n_items) tile = shape->n_items;
+// bytes of scratch with `per_pass` columns per pass (<= 0: the default), -1: refused
+static int64_t rr_scratch_bytes(const PsRtmDesc& D, const RrCols& c, int topk, int64_t per_pass) {
+  int64_t tile = per_pass > 0 ? per_pass : rr_default_tile(D, c.n);
+  if (tile > c.n) tile = c.n;
   RrWs r;
-  if (rr_layout(*desc, *shape, topk, tile, r)) return -1;
+  if (rr_layout(D, c, topk, tile, r)) return -1;
   return r.total * (int64_t)sizeof(float);
 }
-
-// ---- what a call launches: ps_rtm_rank_all and ps_rtm_rank_plan read the same rules
 // items per workgroup: as many as ~48 KB of K / V rows hold (at least one), so several workgroups share a CU
 static int rr_items_per_workgroup(int I, int d, int tile) {
   const size_t per = (size_t)I * 2 * d * sizeof(float);
@@ -601,56 +547,71 @@ static int rr_items_per_workgroup(int I, int d, int tile) {
   it = it < 1 ? 1 : (it > RR_IT_MAX ? RR_IT_MAX : it);
   return it < tile ? it : tile;
 }
-static int rr_epl(const PsRtmDesc& D) { return D.d / 64; }     // columns per lane: the instantiation of the entry / pair kernels
+static int rr_epl(const PsRtmDesc& D) { return D.d / 64; }     // columns per lane: the instantiation of the entry / pair / slot kernels
 static int rr_lph(const PsRtmDesc& D) { return 64 / D.H; }     // lanes per head: the width of a logit's cross-lane sum
 static size_t rr_pair_lds(int IT, int I, int d) { return (size_t)IT * I * 2 * d * sizeof(float); }   // rr_pair_kernel's dynamic LDS
 static bool rr_query_fs_fused(const PsRtmDesc& D) { return D.query_encoder == PS_QENC_FS && ps_fusion_enabled() && D.d <= 128; }
-// the pass size comes from the scratch: the most items whose pairs fit (the layout grows with the tile)
-static int rr_pass_layout(const PsRtmDesc& D, const PsRtmRankShape& Sh, int topk, int64_t scratch_bytes, RrWs& r) {
-  TRY(rr_layout(D, Sh, topk, 1, r));
-  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_all: scratch %lld < %lld bytes (one item per pass)",
-             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
-  int64_t lo = 1, hi = Sh.n_items;
+// the pass size comes from the scratch: the most columns whose pairs fit (the layout grows with the tile)
+static int rr_pass_layout(const PsRtmDesc& D, const RrCols& c, int topk, int64_t scratch_bytes, RrWs& r) {
+  TRY(rr_layout(D, c, topk, 1, r));
+  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "%s: scratch %lld < %lld bytes (one %s per pass)", c.name,
+             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)), c.unit);
+  int64_t lo = 1, hi = c.n;
   while ((int64_t)D.B * hi >= ((int64_t)1 << 30)) hi >>= 1;
   while (lo < hi) {
     const int64_t mid = (lo + hi + 1) / 2;
     RrWs t;
-    if (rr_layout(D, Sh, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
+    if (rr_layout(D, c, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
   }
-  return rr_layout(D, Sh, topk, lo, r);
+  return rr_layout(D, c, topk, lo, r);
 }
-
-extern "C" int ps_rtm_rank_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t scratch_bytes,
-                                PsRtmRankPlan* out) {
-  PS_REQUIRE(desc && shape && out, "rtm rank plan: null argument");
-  memset(out, 0, sizeof(*out));
-  TRY(rr_check(*desc, *shape));
+// the fields the three plans share; `per_pass` is the plan's own name for the pass size
+template <class Plan>
+static int rr_plan(const PsRtmDesc& D, const RrCols& c, int topk, int64_t scratch_bytes, int64_t Plan::*per_pass, Plan* out) {
   RrWs r;
-  TRY(rr_pass_layout(*desc, *shape, topk, scratch_bytes, r));
-  out->items_per_pass = r.tile;
-  out->passes = (shape->n_items + r.tile - 1) / r.tile;
-  out->epl = rr_epl(*desc);
-  out->lph = rr_lph(*desc);
-  out->items_per_workgroup = rr_items_per_workgroup(shape->I, desc->d, r.tile);
-  out->lds_bytes = (int32_t)rr_pair_lds(out->items_per_workgroup, shape->I, desc->d);
+  TRY(rr_pass_layout(D, c, topk, scratch_bytes, r));
+  out->*per_pass = r.tile;
+  out->passes = (c.n + r.tile - 1) / r.tile;
+  out->epl = rr_epl(D);
+  out->lph = rr_lph(D);
   out->tail_fused = r.fuse ? 1 : 0;
-  out->query_fs_fused = rr_query_fs_fused(*desc) ? 1 : 0;
+  out->query_fs_fused = rr_query_fs_fused(D) ? 1 : 0;
   return PS_OK;
 }
 
-template <int EPL>
-static int rr_launch_pair(const RrK& k, hipStream_t st) {
-  const size_t lds = rr_pair_lds(k.IT, k.I, k.d);
-  // (a function attribute is per device: set whenever the tile needs more than the default 64 KB, not once per process)
-  if (lds > 64 * 1024)
-    PS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rr_pair_kernel<EPL>), hipFuncAttributeMaxDynamicSharedMemorySize, RR_LDS_MAX));
-  KTimeScope kt("rtm_rank_pair", st);
-  PS_KLAUNCH((rr_pair_kernel<EPL>), dim3(ps_cdiv(k.tile, k.IT)), dim3(256), lds, st, k);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+// the one dispatch on the columns per lane: f(std::integral_constant<int, EPL>) at the descriptor's EPL
+template <class F>
+static int rr_with_epl(int epl, F&& f) {
+  if (epl == 1) return f(std::integral_constant<int, 1>());
+  if (epl == 2) return f(std::integral_constant<int, 2>());
+  if (epl == 4) return f(std::integral_constant<int, 4>());
+  return f(std::integral_constant<int, 8>());
+}
+// a pass's walk: one wave per (entry, slot) where the columns come from a timeline or from lists, the catalogue's item tiles
+// through LDS otherwise.  The kernel timer's label is the launching entry's.
+static int rr_launch_walk(const RrK& k, int epl, hipStream_t st) {
+  return rr_with_epl(epl, [&](auto E) -> int {
+    constexpr int EPL = decltype(E)::value;
+    if (k.tl_ptr || k.candi) {
+      const dim3 pg(ps_cdiv((int64_t)k.B * k.tile, 4));
+      KTimeScope kt(k.tl_ptr ? "rtm_rank_seq" : "rtm_rank_cand", st);
+      if (k.tl_ptr) PS_KLAUNCH((rr_slot_kernel<EPL, true>), pg, dim3(256), 0, st, k);
+      else PS_KLAUNCH((rr_slot_kernel<EPL, false>), pg, dim3(256), 0, st, k);
+      PS_LAUNCH_CHECK();
+      return PS_OK;
+    }
+    const size_t lds = rr_pair_lds(k.IT, k.I, k.d);
+    // (a function attribute is per device: set whenever the tile needs more than the default 64 KB, not once per process)
+    if (lds > 64 * 1024)
+      PS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rr_pair_kernel<EPL>), hipFuncAttributeMaxDynamicSharedMemorySize, RR_LDS_MAX));
+    KTimeScope kt("rtm_rank_pair", st);
+    PS_KLAUNCH((rr_pair_kernel<EPL>), dim3(ps_cdiv(k.tile, k.IT)), dim3(256), lds, st, k);
+    PS_LAUNCH_CHECK();
+    return PS_OK;
+  });
 }
 
-// ---- the entry side, once per call, for ps_rtm_rank_all and ps_rtm_rank_candidates alike: the shared query encoder (as
+// ---- the entry side, once per call, the same for every launch entry: the shared query encoder (as
 // rtm_encode), the query token, K / V / Q of it, the softmax state over {query, the user's reviews}.  Fills the encoder's view of
 // the tensors and the kernels' arguments for the passes that follow.
 struct RrCall {
@@ -714,12 +675,11 @@ static int rr_entry_side(const PsRtmDesc& D, const PsRtmRankShape& Sh, const PsR
   k.IT = rr_items_per_workgroup(Sh.I, d, r.tile);
   const dim3 eg(ps_cdiv(B, 4));
   c.epl = rr_epl(D);
-  if (c.epl == 1) hipLaunchKernelGGL(rr_entry_kernel<1>, eg, dim3(256), 0, st, k);
-  else if (c.epl == 2) hipLaunchKernelGGL(rr_entry_kernel<2>, eg, dim3(256), 0, st, k);
-  else if (c.epl == 4) hipLaunchKernelGGL(rr_entry_kernel<4>, eg, dim3(256), 0, st, k);
-  else hipLaunchKernelGGL(rr_entry_kernel<8>, eg, dim3(256), 0, st, k);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  return rr_with_epl(c.epl, [&](auto E) -> int {
+    hipLaunchKernelGGL(rr_entry_kernel<decltype(E)::value>, eg, dim3(256), 0, st, k);
+    PS_LAUNCH_CHECK();
+    return PS_OK;
+  });
 }
 static int rr_tensor_check(const PsRtmDesc& D, const PsRtmTensors& P) {
   TRY(rr_layer_check(P));
@@ -731,79 +691,99 @@ static int rr_tensor_check(const PsRtmDesc& D, const PsRtmTensors& P) {
   return PS_OK;
 }
 
+// what every launch entry asks of its arguments after its own null checks, under its own name
+static int rr_call_check(const char* name, const PsRtmDesc& D, const PsRtmRankShape& Sh, const PsRtmTensors& P, const int32_t* rank,
+                         const int64_t* target_prod_idxs, const void* scratch) {
+  TRY(rr_check(D, Sh));
+  PS_REQUIRE(!rank || target_prod_idxs, "%s: rank needs target_prod_idxs", name);
+  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "%s: scratch must be 256-byte aligned", name);
+  return rr_tensor_check(D, P);
+}
+
+// ---- THE driver of the three launch entries: the entry side, then passes over tiles of the columns — the walk (item tiles of
+// the catalogue through LDS, or one wave per slot) -> the encoder's per-replica tail (n_in = B, fan = tile) -> head — and the
+// selection.  `item_ridxs` [P, I] the static lists (null with a timeline), `candi` [B, cols.n] the entries' lists (null: the
+// columns are the catalogue rows), `tl` / `stamps` the time-ordered evaluation's (null otherwise).
+struct RrSrc { const int64_t *item_ridxs, *candi; const PsRtmSeqTimeline* tl; const int64_t* stamps; };
+static int rr_run(const PsRtmDesc& D, const PsRtmRankShape& Sh, const PsRtmTensors& P, const float* index, const RrSrc& src, const RrCols& cols,
+                  const int64_t* query_word_idxs, const int64_t* u_ridxs, const int64_t* target_prod_idxs, int32_t topk, int64_t* top_idx,
+                  float* top_score, int32_t* rank, float* scores_out, void* scratch, int64_t scratch_bytes, ps_stream_t stream) {
+  const int B = D.B, d = D.d;
+  const int64_t N = cols.n;
+  RrWs r;
+  TRY(rr_pass_layout(D, cols, topk, scratch_bytes, r));
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = reinterpret_cast<float*>(scratch);
+  RrCall c;
+  TRY(rr_entry_side(D, Sh, P, index, src.item_ridxs, query_word_idxs, u_ridxs, r, ws, st, c));
+  RrK& k = c.k;
+  k.candi = src.candi; k.C = cols.list ? (int)N : 0;
+  if (src.tl) { k.tl_ptr = src.tl->ptr; k.tl_rids = src.tl->rids; k.tl_times = src.tl->times; k.tl_n = src.tl->n; k.stamps = src.stamps; }
+  float* S = ws + r.S;
+  for (int64_t c0 = 0; c0 < N; c0 += r.tile) {
+    k.i0 = (int)c0;
+    k.nv = (int)(c0 + r.tile <= N ? r.tile : N - c0);
+    TRY(rr_launch_walk(k, c.epl, st));
+    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
+    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
+    hipLaunchKernelGGL(rr_head_kernel, dim3(ps_cdiv((int64_t)B * r.tile, 4)), dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, src.candi, B,
+                       r.tile, k.nv, d, k.i0, k.C, k.P, k.ldS, S);
+    PS_LAUNCH_CHECK();
+  }
+  if (scores_out)
+    PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)N * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)N * sizeof(float),
+                                  (size_t)B, hipMemcpyDeviceToDevice, st));
+  // ---- the selection is rank.hip's: over the catalogue rows, or over [B, C] with the columns as ids — the target's column
+  // first, the columns -> item ids after
+  if (!cols.list) return rank_select_scores(S, r.ldS, B, N, target_prod_idxs, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st);
+  int64_t* tcol = reinterpret_cast<int64_t*>(ws + r.tcol);
+  if (target_prod_idxs) {
+    hipLaunchKernelGGL(rr_cand_target_kernel, dim3(ps_cdiv(B, 4)), dim3(256), 0, st, src.candi, target_prod_idxs, B, (int)N, k.P, tcol);
+    PS_LAUNCH_CHECK();
+  }
+  TRY(rank_select_scores(S, r.ldS, B, N, target_prod_idxs ? tcol : nullptr, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st));
+  hipLaunchKernelGGL(rr_cand_ids_kernel, dim3(ps_cdiv((int64_t)B * topk, 256)), dim3(256), 0, st, src.candi, B, (int)N, topk, top_idx,
+                     top_score);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// ------------------------------------------------------------------ the whole catalogue (ps_rtm_rank_scratch_bytes / _plan / _all)
+extern "C" int64_t ps_rtm_rank_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t items_per_pass) {
+  if (!desc || !shape) { ps_set_error("rtm rank scratch: null argument"); return -1; }
+  if (rr_check(*desc, *shape)) return -1;
+  return rr_scratch_bytes(*desc, rr_all_cols(*shape), topk, items_per_pass);
+}
+
+extern "C" int ps_rtm_rank_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int32_t topk, int64_t scratch_bytes,
+                                PsRtmRankPlan* out) {
+  PS_REQUIRE(desc && shape && out, "rtm rank plan: null argument");
+  memset(out, 0, sizeof(*out));
+  TRY(rr_check(*desc, *shape));
+  TRY(rr_plan(*desc, rr_all_cols(*shape), topk, scratch_bytes, &PsRtmRankPlan::items_per_pass, out));
+  out->items_per_workgroup = rr_items_per_workgroup(shape->I, desc->d, (int)out->items_per_pass);
+  out->lds_bytes = (int32_t)rr_pair_lds(out->items_per_workgroup, shape->I, desc->d);
+  return PS_OK;
+}
+
 extern "C" int ps_rtm_rank_all(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
                                const int64_t* item_ridxs, const int64_t* query_word_idxs, const int64_t* u_ridxs,
                                const int64_t* target_prod_idxs, int32_t topk, int64_t* top_idx, float* top_score, int32_t* rank,
                                float* scores_out, void* scratch, int64_t scratch_bytes, ps_stream_t stream) {
   PS_REQUIRE(desc && shape && params && index && item_ridxs && query_word_idxs && u_ridxs && top_idx && top_score && scratch,
              "rtm rank_all: null argument");
-  const PsRtmDesc& D = *desc;
-  const PsRtmRankShape& Sh = *shape;
-  const PsRtmTensors& P = *params;
-  TRY(rr_check(D, Sh));
-  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_all: rank needs target_prod_idxs");
-  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_all: scratch must be 256-byte aligned");
-  TRY(rr_tensor_check(D, P));
-  const int B = D.B, d = D.d;
-  const int64_t NP = Sh.n_items;
-  RrWs r;
-  TRY(rr_pass_layout(D, Sh, topk, scratch_bytes, r));
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = reinterpret_cast<float*>(scratch);
-  RrCall c;
-  TRY(rr_entry_side(D, Sh, P, index, item_ridxs, query_word_idxs, u_ridxs, r, ws, st, c));
-  RrK& k = c.k;
-  // ---- passes over item tiles: pair kernel -> the encoder's per-replica tail (n_in = B, fan = tile) -> head
-  float* S = ws + r.S;
-  for (int64_t i0 = 0; i0 < NP; i0 += r.tile) {
-    k.i0 = (int)i0;
-    k.nv = (int)(i0 + r.tile <= NP ? r.tile : NP - i0);
-    if (c.epl == 1) TRY(rr_launch_pair<1>(k, st));
-    else if (c.epl == 2) TRY(rr_launch_pair<2>(k, st));
-    else if (c.epl == 4) TRY(rr_launch_pair<4>(k, st));
-    else TRY(rr_launch_pair<8>(k, st));
-    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
-    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
-    hipLaunchKernelGGL(rr_head_kernel, dim3(ps_cdiv((int64_t)B * r.tile, 4)), dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, B, r.tile,
-                       k.nv, d, k.i0, k.ldS, S);
-    PS_LAUNCH_CHECK();
-  }
-  if (scores_out)
-    PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)NP * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)NP * sizeof(float),
-                                  (size_t)B, hipMemcpyDeviceToDevice, st));
-  return rank_select_scores(S, r.ldS, B, NP, target_prod_idxs, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st);
+  TRY(rr_call_check("rtm rank_all", *desc, *shape, *params, rank, target_prod_idxs, scratch));
+  return rr_run(*desc, *shape, *params, index, RrSrc{item_ridxs, nullptr, nullptr, nullptr}, rr_all_cols(*shape), query_word_idxs, u_ridxs,
+                target_prod_idxs, topk, top_idx, top_score, rank, scores_out, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------ per-entry candidate lists (ps_rtm_rank_cand_*, ps_rtm_rank_candidates)
-static int64_t rr_cand_default_tile(const PsRtmDesc& D, int64_t C) {
-  int64_t t = RR_PASS_PAIRS / D.B;
-  t = t < 1 ? 1 : t;
-  return t < C ? t : C;
-}
-// the pass size comes from the scratch, as rr_pass_layout takes it: the most columns of the list whose pairs fit
-static int rr_cand_pass_layout(const PsRtmDesc& D, int64_t C, int topk, int64_t scratch_bytes, RrWs& r) {
-  TRY(rr_cand_layout(D, C, topk, 1, r));
-  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_candidates: scratch %lld < %lld bytes (one candidate per pass)",
-             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
-  int64_t lo = 1, hi = C;
-  while ((int64_t)D.B * hi >= ((int64_t)1 << 30)) hi >>= 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) / 2;
-    RrWs t;
-    if (rr_cand_layout(D, C, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
-  }
-  return rr_cand_layout(D, C, topk, lo, r);
-}
-
 extern "C" int64_t ps_rtm_rank_cand_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk,
                                                   int64_t cands_per_pass) {
   if (!desc || !shape) { ps_set_error("rtm rank_candidates scratch: null argument"); return -1; }
-  if (rr_check(*desc, *shape)) return -1;
-  int64_t tile = cands_per_pass > 0 ? cands_per_pass : rr_cand_default_tile(*desc, C);
-  if (tile > C && C >= 1) tile = C;
-  RrWs r;
-  if (rr_cand_layout(*desc, C, topk, tile, r)) return -1;
-  return r.total * (int64_t)sizeof(float);
+  RrCols cols;
+  if (rr_check(*desc, *shape) || rr_cand_cols(C, cols)) return -1;
+  return rr_scratch_bytes(*desc, cols, topk, cands_per_pass);
 }
 
 extern "C" int ps_rtm_rank_cand_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk, int64_t scratch_bytes,
@@ -811,15 +791,9 @@ extern "C" int ps_rtm_rank_cand_plan(const PsRtmDesc* desc, const PsRtmRankShape
   PS_REQUIRE(desc && shape && out, "rtm rank_candidates plan: null argument");
   memset(out, 0, sizeof(*out));
   TRY(rr_check(*desc, *shape));
-  RrWs r;
-  TRY(rr_cand_pass_layout(*desc, C, topk, scratch_bytes, r));
-  out->cands_per_pass = r.tile;
-  out->passes = (C + r.tile - 1) / r.tile;
-  out->epl = rr_epl(*desc);
-  out->lph = rr_lph(*desc);
-  out->tail_fused = r.fuse ? 1 : 0;
-  out->query_fs_fused = rr_query_fs_fused(*desc) ? 1 : 0;
-  return PS_OK;
+  RrCols cols;
+  TRY(rr_cand_cols(C, cols));
+  return rr_plan(*desc, cols, topk, scratch_bytes, &PsRtmRankCandPlan::cands_per_pass, out);
 }
 
 extern "C" int ps_rtm_rank_candidates(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
@@ -829,100 +803,25 @@ extern "C" int ps_rtm_rank_candidates(const PsRtmDesc* desc, const PsRtmRankShap
                                       int64_t scratch_bytes, ps_stream_t stream) {
   PS_REQUIRE(desc && shape && params && index && item_ridxs && query_word_idxs && u_ridxs && candi_prod_idxs && top_idx && top_score && scratch,
              "rtm rank_candidates: null argument");
-  const PsRtmDesc& D = *desc;
-  const PsRtmRankShape& Sh = *shape;
-  const PsRtmTensors& P = *params;
-  TRY(rr_check(D, Sh));
-  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_candidates: rank needs target_prod_idxs");
-  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_candidates: scratch must be 256-byte aligned");
-  TRY(rr_tensor_check(D, P));
-  const int B = D.B, d = D.d;
-  RrWs r;
-  TRY(rr_cand_pass_layout(D, C, topk, scratch_bytes, r));
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = reinterpret_cast<float*>(scratch);
-  RrCall c;
-  TRY(rr_entry_side(D, Sh, P, index, item_ridxs, query_word_idxs, u_ridxs, r, ws, st, c));
-  RrK& k = c.k;
-  k.candi = candi_prod_idxs; k.C = (int)C;
-  // ---- passes over column tiles of the lists: candidate kernel -> the encoder's per-replica tail (n_in = B, fan = tile) -> head
-  float* S = ws + r.S;
-  const dim3 pg(ps_cdiv((int64_t)B * r.tile, 4));
-  for (int64_t c0 = 0; c0 < C; c0 += r.tile) {
-    k.i0 = (int)c0;
-    k.nv = (int)(c0 + r.tile <= C ? r.tile : C - c0);
-    {
-      KTimeScope kt("rtm_rank_cand", st);
-      if (c.epl == 1) PS_KLAUNCH((rr_cand_kernel<1>), pg, dim3(256), 0, st, k);
-      else if (c.epl == 2) PS_KLAUNCH((rr_cand_kernel<2>), pg, dim3(256), 0, st, k);
-      else if (c.epl == 4) PS_KLAUNCH((rr_cand_kernel<4>), pg, dim3(256), 0, st, k);
-      else PS_KLAUNCH((rr_cand_kernel<8>), pg, dim3(256), 0, st, k);
-      PS_LAUNCH_CHECK();
-    }
-    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
-    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
-    hipLaunchKernelGGL(rr_cand_head_kernel, pg, dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, candi_prod_idxs, B, r.tile, k.nv, d, k.i0,
-                       k.C, k.P, k.ldS, S);
-    PS_LAUNCH_CHECK();
-  }
-  if (scores_out)
-    PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)C * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)C * sizeof(float),
-                                  (size_t)B, hipMemcpyDeviceToDevice, st));
-  // ---- the selection is rank.hip's over [B, C] with the columns as ids: the target's column first, the columns -> item ids after
-  int64_t* tcol = reinterpret_cast<int64_t*>(ws + r.tcol);
-  if (target_prod_idxs) {
-    hipLaunchKernelGGL(rr_cand_target_kernel, dim3(ps_cdiv(B, 4)), dim3(256), 0, st, candi_prod_idxs, target_prod_idxs, B, (int)C, k.P, tcol);
-    PS_LAUNCH_CHECK();
-  }
-  TRY(rank_select_scores(S, r.ldS, B, C, target_prod_idxs ? tcol : nullptr, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st));
-  hipLaunchKernelGGL(rr_cand_ids_kernel, dim3(ps_cdiv((int64_t)B * topk, 256)), dim3(256), 0, st, candi_prod_idxs, B, (int)C, topk, top_idx,
-                     top_score);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  TRY(rr_call_check("rtm rank_candidates", *desc, *shape, *params, rank, target_prod_idxs, scratch));
+  RrCols cols;
+  TRY(rr_cand_cols(C, cols));
+  return rr_run(*desc, *shape, *params, index, RrSrc{item_ridxs, candi_prod_idxs, nullptr, nullptr}, cols, query_word_idxs, u_ridxs,
+                target_prod_idxs, topk, top_idx, top_score, rank, scores_out, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------ the time-ordered evaluation (ps_rtm_rank_seq*)
-// The columns are the slots of the entries' lists (C of them) or, with no list, the P catalogue rows.  The shape's seq_review_test
-// says what the run is and is not a refusal here: rr_check sees the shape with the field cleared.
+// The shape's seq_review_test says what the run is and is not a refusal here: rr_check sees the shape with the field cleared.
+// (The host-only entries have no list pointer to look at: C = PS_RTM_SEQ_NO_LIST names the catalogue form there.)
 static PsRtmRankShape rr_seq_shape(const PsRtmRankShape& S) { PsRtmRankShape s = S; s.seq_review_test = 0; return s; }
-static int rr_seq_layout(const PsRtmDesc& D, int64_t cols, bool list, int topk, int64_t tile, RrWs& r) {
-  PS_REQUIRE(!list || cols >= 1, "rtm rank_seq: %lld candidates per entry (at least 1)", (long long)cols);
-  PS_REQUIRE(cols >= 1 && cols < ((int64_t)1 << 31), "rtm rank_seq: %lld columns", (long long)cols);
-  PS_REQUIRE(tile >= 1 && tile <= cols && (int64_t)D.B * tile < ((int64_t)1 << 30), "rtm rank_seq: %lld slots per pass", (long long)tile);
-  TRY(rr_layout_cols(D, cols, topk, tile, "rtm rank_seq", r));
-  int64_t cur = r.total;
-  r.tcol = rtake(cur, 2 * (int64_t)D.B);
-  r.total = cur;
-  return PS_OK;
-}
-static int rr_seq_pass_layout(const PsRtmDesc& D, int64_t cols, bool list, int topk, int64_t scratch_bytes, RrWs& r) {
-  TRY(rr_seq_layout(D, cols, list, topk, 1, r));
-  PS_REQUIRE(r.total * (int64_t)sizeof(float) <= scratch_bytes, "rtm rank_seq: scratch %lld < %lld bytes (one slot per pass)",
-             (long long)scratch_bytes, (long long)(r.total * (int64_t)sizeof(float)));
-  int64_t lo = 1, hi = cols;
-  while ((int64_t)D.B * hi >= ((int64_t)1 << 30)) hi >>= 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) / 2;
-    RrWs t;
-    if (rr_seq_layout(D, cols, list, topk, mid, t) == PS_OK && t.total * (int64_t)sizeof(float) <= scratch_bytes) lo = mid; else hi = mid - 1;
-  }
-  return rr_seq_layout(D, cols, list, topk, lo, r);
-}
-// (the host-only entries have no list pointer to look at: C = PS_RTM_SEQ_NO_LIST names the catalogue form there)
-static int64_t rr_seq_cols(const PsRtmRankShape& S, int64_t C, bool list) { return list ? C : S.n_items; }
 
 extern "C" int64_t ps_rtm_rank_seq_scratch_bytes(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk,
                                                  int64_t slots_per_pass) {
   if (!desc || !shape) { ps_set_error("rtm rank_seq scratch: null argument"); return -1; }
   const PsRtmRankShape Sh = rr_seq_shape(*shape);
-  if (rr_check(*desc, Sh)) return -1;
-  const bool list = C != PS_RTM_SEQ_NO_LIST;
-  const int64_t cols = rr_seq_cols(Sh, C, list);
-  int64_t tile = slots_per_pass > 0 ? slots_per_pass : rr_cand_default_tile(*desc, cols);
-  if (tile > cols && cols >= 1) tile = cols;
-  RrWs r;
-  if (rr_seq_layout(*desc, cols, list, topk, tile, r)) return -1;
-  return r.total * (int64_t)sizeof(float);
+  RrCols cols;
+  if (rr_check(*desc, Sh) || rr_seq_cols(Sh, C, C != PS_RTM_SEQ_NO_LIST, cols)) return -1;
+  return rr_scratch_bytes(*desc, cols, topk, slots_per_pass);
 }
 
 extern "C" int ps_rtm_rank_seq_plan(const PsRtmDesc* desc, const PsRtmRankShape* shape, int64_t C, int32_t topk, int64_t scratch_bytes,
@@ -931,17 +830,9 @@ extern "C" int ps_rtm_rank_seq_plan(const PsRtmDesc* desc, const PsRtmRankShape*
   memset(out, 0, sizeof(*out));
   const PsRtmRankShape Sh = rr_seq_shape(*shape);
   TRY(rr_check(*desc, Sh));
-  const bool list = C != PS_RTM_SEQ_NO_LIST;
-  const int64_t cols = rr_seq_cols(Sh, C, list);
-  RrWs r;
-  TRY(rr_seq_pass_layout(*desc, cols, list, topk, scratch_bytes, r));
-  out->slots_per_pass = r.tile;
-  out->passes = (cols + r.tile - 1) / r.tile;
-  out->epl = rr_epl(*desc);
-  out->lph = rr_lph(*desc);
-  out->tail_fused = r.fuse ? 1 : 0;
-  out->query_fs_fused = rr_query_fs_fused(*desc) ? 1 : 0;
-  return PS_OK;
+  RrCols cols;
+  TRY(rr_seq_cols(Sh, C, C != PS_RTM_SEQ_NO_LIST, cols));
+  return rr_plan(*desc, cols, topk, scratch_bytes, &PsRtmRankSeqPlan::slots_per_pass, out);
 }
 
 extern "C" int ps_rtm_rank_seq(const PsRtmDesc* desc, const PsRtmRankShape* shape, const PsRtmTensors* params, const float* index,
@@ -953,61 +844,10 @@ extern "C" int ps_rtm_rank_seq(const PsRtmDesc* desc, const PsRtmRankShape* shap
              "rtm rank_seq: null argument");
   PS_REQUIRE(timeline && timeline->ptr && timeline->rids && timeline->times, "rtm rank_seq: null timeline");
   PS_REQUIRE(timeline->n >= 1, "rtm rank_seq: a timeline of %lld reviews (at least 1)", (long long)timeline->n);
-  const PsRtmDesc& D = *desc;
   const PsRtmRankShape Sh = rr_seq_shape(*shape);
-  const PsRtmTensors& P = *params;
-  TRY(rr_check(D, Sh));
-  PS_REQUIRE(!rank || target_prod_idxs, "rtm rank_seq: rank needs target_prod_idxs");
-  PS_REQUIRE((((uintptr_t)scratch) & 255) == 0, "rtm rank_seq: scratch must be 256-byte aligned");
-  TRY(rr_tensor_check(D, P));
-  const bool list = candi_prod_idxs != nullptr;
-  const int B = D.B, d = D.d;
-  const int64_t cols = rr_seq_cols(Sh, C, list);
-  RrWs r;
-  TRY(rr_seq_pass_layout(D, cols, list, topk, scratch_bytes, r));
-  hipStream_t st = (hipStream_t)stream;
-  float* ws = reinterpret_cast<float*>(scratch);
-  RrCall c;
-  TRY(rr_entry_side(D, Sh, P, index, nullptr, query_word_idxs, u_ridxs, r, ws, st, c));
-  RrK& k = c.k;
-  k.candi = candi_prod_idxs; k.C = list ? (int)C : 0;
-  k.tl_ptr = timeline->ptr; k.tl_rids = timeline->rids; k.tl_times = timeline->times; k.tl_n = timeline->n; k.stamps = time_stamps;
-  // ---- passes over column tiles: window + walk -> the encoder's per-replica tail (n_in = B, fan = tile) -> head
-  float* S = ws + r.S;
-  const dim3 pg(ps_cdiv((int64_t)B * r.tile, 4));
-  for (int64_t c0 = 0; c0 < cols; c0 += r.tile) {
-    k.i0 = (int)c0;
-    k.nv = (int)(c0 + r.tile <= cols ? r.tile : cols - c0);
-    {
-      KTimeScope kt("rtm_rank_seq", st);
-      if (c.epl == 1) PS_KLAUNCH((rr_seq_kernel<1>), pg, dim3(256), 0, st, k);
-      else if (c.epl == 2) PS_KLAUNCH((rr_seq_kernel<2>), pg, dim3(256), 0, st, k);
-      else if (c.epl == 4) PS_KLAUNCH((rr_seq_kernel<4>), pg, dim3(256), 0, st, k);
-      else PS_KLAUNCH((rr_seq_kernel<8>), pg, dim3(256), 0, st, k);
-      PS_LAUNCH_CHECK();
-    }
-    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
-    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
-    if (list)
-      hipLaunchKernelGGL(rr_cand_head_kernel, pg, dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, candi_prod_idxs, B, r.tile, k.nv, d, k.i0,
-                         k.C, k.P, k.ldS, S);
-    else
-      hipLaunchKernelGGL(rr_head_kernel, pg, dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, B, r.tile, k.nv, d, k.i0, k.ldS, S);
-    PS_LAUNCH_CHECK();
-  }
-  if (scores_out)
-    PS_CHECK_HIP(hipMemcpy2DAsync(scores_out, (size_t)cols * sizeof(float), S, (size_t)r.ldS * sizeof(float), (size_t)cols * sizeof(float),
-                                  (size_t)B, hipMemcpyDeviceToDevice, st));
-  // ---- the selection: ps_rtm_rank_all's over the catalogue rows, ps_rtm_rank_candidates' over the columns of the lists
-  if (!list) return rank_select_scores(S, r.ldS, B, cols, target_prod_idxs, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st);
-  int64_t* tcol = reinterpret_cast<int64_t*>(ws + r.tcol);
-  if (target_prod_idxs) {
-    hipLaunchKernelGGL(rr_cand_target_kernel, dim3(ps_cdiv(B, 4)), dim3(256), 0, st, candi_prod_idxs, target_prod_idxs, B, (int)C, k.P, tcol);
-    PS_LAUNCH_CHECK();
-  }
-  TRY(rank_select_scores(S, r.ldS, B, C, target_prod_idxs ? tcol : nullptr, topk, top_idx, top_score, rank, ws + r.sel, r.sel_bytes, st));
-  hipLaunchKernelGGL(rr_cand_ids_kernel, dim3(ps_cdiv((int64_t)B * topk, 256)), dim3(256), 0, st, candi_prod_idxs, B, (int)C, topk, top_idx,
-                     top_score);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  TRY(rr_call_check("rtm rank_seq", *desc, Sh, *params, rank, target_prod_idxs, scratch));
+  RrCols cols;
+  TRY(rr_seq_cols(Sh, C, candi_prod_idxs != nullptr, cols));
+  return rr_run(*desc, Sh, *params, index, RrSrc{nullptr, candi_prod_idxs, timeline, time_stamps}, cols, query_word_idxs, u_ridxs,
+                target_prod_idxs, topk, top_idx, top_score, rank, scores_out, scratch, scratch_bytes, stream);
 }

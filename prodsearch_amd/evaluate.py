@@ -116,6 +116,57 @@ def rank_all(model, batch, topk=100):
     return top_idx, top_score, rank
 
 
+def _rank_rtm(fn, model, index, batch, topk, return_scores, attr, extra, shapes, nbytes, launch, width, timeline=False):
+    """The common work of ``rank_all_rtm`` / ``rank_candidates_rtm`` / ``rank_seq_rtm`` (``fn`` in the messages): refusal, the
+    index's owner and staleness, the batch's fields, the descriptor, a scratch of exactly the entry's size cached on the model
+    under ``attr``, the outputs.  What differs comes from the caller: ``extra`` — its further batch fields as (name, dims,
+    required), [B, ...] each — and ``shapes``, the shape refusal's wording; ``nbytes(lib, desc, sh, k, *x)`` the entry's
+    ``*_scratch_bytes``, ``width(*x)`` the columns of the dense scores and ``launch(lib, head, qw, ur, target, tail, *x)``
+    the entry itself, with ``x`` the extra fields' tensors (None for an absent optional one), ``head`` = (desc, shape,
+    tensors, index) and ``tail`` = (topk, top_idx, top_score, rank, scores, scratch, its bytes, stream)."""
+    kind = 'timeline' if timeline else 'catalogue'
+    msg = model._rank_all_refusal(time_ordered=timeline)
+    if msg is not None:
+        raise NotImplementedError(msg)
+    if index.model is not model:
+        raise RuntimeError("%s: the %s index belongs to another model" % (fn, kind))
+    if index.stale():
+        raise RuntimeError("%s: stale %s index — a weight, a table or the %s changed since "
+                           "model.%s_index() built it; build it again" % (fn, kind, kind, kind))
+    for name, _, required in extra:
+        if required and getattr(batch, name, None) is None:
+            raise RuntimeError("%s: the batch carries no %s" % (fn, name))
+    lib = _lib.load()
+    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
+    ur = model._idx(batch.u_ridxs, 'u_ridxs')
+    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
+    x = [model._idx(getattr(batch, name, None), name) for name, _, _ in extra]
+    B, Q = qw.shape
+    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,) or \
+            any(t is not None and (t.dim() != dims or t.shape[0] != B) for t, (_, dims, _) in zip(x, extra)):
+        raise RuntimeError("%s: %s" % (fn, shapes))
+    ps, _ = model._structs()
+    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
+    k = int(topk)
+    dev = qw.device
+    n = nbytes(lib, desc, sh, k, *x)
+    if n < 0:
+        raise RuntimeError("%s: %s" % (fn, lib.ps_last_error().decode('utf-8', 'replace')))
+    # exactly n bytes: the C entry sizes its passes from the scratch it is given, so the buffer is part of the result's shape
+    scratch = model.__dict__.get(attr)
+    if scratch is None or scratch.numel() != n or scratch.device != dev:
+        scratch = model.__dict__[attr] = torch.empty(n, dtype=torch.uint8, device=dev)
+    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, width(*x), dtype=torch.float32, device=dev) if return_scores else None
+    head = (desc, sh, ps, index.index.data_ptr())
+    tail = (k, top_idx.data_ptr(), top_score.data_ptr(), rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(), scratch.numel(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    launch(lib, head, qw.data_ptr(), ur.data_ptr(), target.data_ptr(), tail, *x)
+    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+
+
 def rank_all_rtm(model, index, batch, topk=100, items_per_pass=None, return_scores=False):
     """The review transformer over the whole catalogue (``ps_rtm_rank_all``): what ``Trainer.test`` gets from
     ``model.test`` over chunks of all products plus the host-side ranking, without encoding every (entry, candidate) sequence.
@@ -123,42 +174,13 @@ def rank_all_rtm(model, index, batch, topk=100, items_per_pass=None, return_scor
     ``query_word_idxs`` [B,Q], ``u_ridxs`` [B,U], ``target_prod_idxs`` [B], on the device).  ``items_per_pass``: bound the
     workspace (default: 32768 pairs per pass).  -> (top_idx [B,k] int64, top_score [B,k], rank [B] int32) as ``rank_all``
     (+ the dense scores [B,P] with ``return_scores``)."""
-    msg = model._rank_all_refusal()
-    if msg is not None:
-        raise NotImplementedError(msg)
-    if index.model is not model:
-        raise RuntimeError("rank_all_rtm: the catalogue index belongs to another model")
-    if index.stale():
-        raise RuntimeError("rank_all_rtm: stale catalogue index — a weight, a table or the catalogue changed since "
-                           "model.catalogue_index() built it; build it again")
-    lib = _lib.load()
-    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
-    ur = model._idx(batch.u_ridxs, 'u_ridxs')
-    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
-    B, Q = qw.shape
-    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,):
-        raise RuntimeError("rank_all_rtm: u_ridxs must be [B, U] and target_prod_idxs [B]")
-    ps, _ = model._structs()
-    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
-    k = int(topk)
-    dev = qw.device
-    nbytes = lib.ps_rtm_rank_scratch_bytes(desc, sh, k, int(items_per_pass or 0))
-    if nbytes < 0:
-        raise RuntimeError("rank_all_rtm: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
-    # exactly nbytes: the C entry sizes its passes from the scratch it is given, so the buffer is part of the result's shape
-    scratch = model.__dict__.get('_rtm_rank_scratch')
-    if scratch is None or scratch.numel() != nbytes or scratch.device != dev:
-        scratch = model.__dict__['_rtm_rank_scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    P = index.shape3[0]
-    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
-    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
-    rank = torch.empty(B, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, P, dtype=torch.float32, device=dev) if return_scores else None
-    _lib.check(lib.ps_rtm_rank_all(desc, sh, ps, index.index.data_ptr(), index.item_ridxs.data_ptr(), qw.data_ptr(),
-                                   ur.data_ptr(), target.data_ptr(), k, top_idx.data_ptr(), top_score.data_ptr(),
-                                   rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(), scratch.numel(),
-                                   torch.cuda.current_stream(dev).cuda_stream), 'ps_rtm_rank_all')
-    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+    return _rank_rtm(
+        'rank_all_rtm', model, index, batch, topk, return_scores, '_rtm_rank_scratch',
+        (), "u_ridxs must be [B, U] and target_prod_idxs [B]",
+        lambda lib, desc, sh, k: lib.ps_rtm_rank_scratch_bytes(desc, sh, k, int(items_per_pass or 0)),
+        lambda lib, head, qw, ur, target, tail: _lib.check(
+            lib.ps_rtm_rank_all(*head, index.item_ridxs.data_ptr(), qw, ur, target, *tail), 'ps_rtm_rank_all'),
+        lambda: index.shape3[0])
 
 
 def rank_candidates_rtm(model, index, batch, topk=100, cands_per_pass=None, return_scores=False):
@@ -169,44 +191,14 @@ def rank_candidates_rtm(model, index, batch, topk=100, cands_per_pass=None, retu
     ragged list, is dead).  -> (top_idx [B,k] ITEM ids of the live slots by (score desc, column asc), -1 where unfilled;
     top_score [B,k]; rank [B] int32: 1 + the live slots ahead of the first column holding the target, 0 = not in the list)
     (+ the dense scores [B,C], -inf at dead slots, with ``return_scores``)."""
-    msg = model._rank_all_refusal()
-    if msg is not None:
-        raise NotImplementedError(msg)
-    if index.model is not model:
-        raise RuntimeError("rank_candidates_rtm: the catalogue index belongs to another model")
-    if index.stale():
-        raise RuntimeError("rank_candidates_rtm: stale catalogue index — a weight, a table or the catalogue changed since "
-                           "model.catalogue_index() built it; build it again")
-    if getattr(batch, 'candi_prod_idxs', None) is None:
-        raise RuntimeError("rank_candidates_rtm: the batch carries no candi_prod_idxs")
-    lib = _lib.load()
-    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
-    ur = model._idx(batch.u_ridxs, 'u_ridxs')
-    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
-    cand = model._idx(batch.candi_prod_idxs, 'candi_prod_idxs')
-    B, Q = qw.shape
-    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,) or cand.dim() != 2 or cand.shape[0] != B:
-        raise RuntimeError("rank_candidates_rtm: u_ridxs must be [B, U], target_prod_idxs [B] and candi_prod_idxs [B, C]")
-    ps, _ = model._structs()
-    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
-    k, C = int(topk), int(cand.shape[1])
-    dev = qw.device
-    nbytes = lib.ps_rtm_rank_cand_scratch_bytes(desc, sh, C, k, int(cands_per_pass or 0))
-    if nbytes < 0:
-        raise RuntimeError("rank_candidates_rtm: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
-    # exactly nbytes, as rank_all_rtm: the C entry sizes its passes from the scratch it is given
-    scratch = model.__dict__.get('_rtm_rank_cand_scratch')
-    if scratch is None or scratch.numel() != nbytes or scratch.device != dev:
-        scratch = model.__dict__['_rtm_rank_cand_scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
-    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
-    rank = torch.empty(B, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, C, dtype=torch.float32, device=dev) if return_scores else None
-    _lib.check(lib.ps_rtm_rank_candidates(desc, sh, ps, index.index.data_ptr(), index.item_ridxs.data_ptr(), qw.data_ptr(),
-                                          ur.data_ptr(), cand.data_ptr(), C, target.data_ptr(), k, top_idx.data_ptr(),
-                                          top_score.data_ptr(), rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(),
-                                          scratch.numel(), torch.cuda.current_stream(dev).cuda_stream), 'ps_rtm_rank_candidates')
-    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+    return _rank_rtm(
+        'rank_candidates_rtm', model, index, batch, topk, return_scores, '_rtm_rank_cand_scratch',
+        (('candi_prod_idxs', 2, True),), "u_ridxs must be [B, U], target_prod_idxs [B] and candi_prod_idxs [B, C]",
+        lambda lib, desc, sh, k, cand: lib.ps_rtm_rank_cand_scratch_bytes(desc, sh, cand.shape[1], k, int(cands_per_pass or 0)),
+        lambda lib, head, qw, ur, target, tail, cand: _lib.check(
+            lib.ps_rtm_rank_candidates(*head, index.item_ridxs.data_ptr(), qw, ur, cand.data_ptr(), cand.shape[1], target, *tail),
+            'ps_rtm_rank_candidates'),
+        lambda cand: cand.shape[1])
 
 
 def rank_seq_rtm(model, index, batch, topk=100, slots_per_pass=None, return_scores=False):
@@ -216,48 +208,17 @@ def rank_seq_rtm(model, index, batch, topk=100, slots_per_pass=None, return_scor
     ``ProdSearchRankBatch`` with ``time_stamps`` [B] (``ProdSearchDataLoader.seq_rank_batches`` / ``seq_candidate_batches``).
     With ``candi_prod_idxs`` [B, C] the result is ``rank_candidates_rtm``'s over the lists, without them ``rank_all_rtm``'s
     over the catalogue (+ the dense scores [B, C] / [B, P] with ``return_scores``)."""
-    msg = model._rank_all_refusal(time_ordered=True)
-    if msg is not None:
-        raise NotImplementedError(msg)
-    if index.model is not model:
-        raise RuntimeError("rank_seq_rtm: the timeline index belongs to another model")
-    if index.stale():
-        raise RuntimeError("rank_seq_rtm: stale timeline index — a weight, a table or the timeline changed since "
-                           "model.timeline_index() built it; build it again")
-    if getattr(batch, 'time_stamps', None) is None:
-        raise RuntimeError("rank_seq_rtm: the batch carries no time_stamps")
-    lib = _lib.load()
-    qw = model._idx(batch.query_word_idxs, 'query_word_idxs')
-    ur = model._idx(batch.u_ridxs, 'u_ridxs')
-    target = model._idx(batch.target_prod_idxs, 'target_prod_idxs')
-    stamps = model._idx(batch.time_stamps, 'time_stamps')
-    cand = model._idx(getattr(batch, 'candi_prod_idxs', None), 'candi_prod_idxs')
-    B, Q = qw.shape
-    if ur.dim() != 2 or ur.shape[0] != B or target.shape != (B,) or stamps.shape != (B,) or \
-            (cand is not None and (cand.dim() != 2 or cand.shape[0] != B)):
-        raise RuntimeError("rank_seq_rtm: u_ridxs must be [B, U], target_prod_idxs and time_stamps [B], candi_prod_idxs [B, C]")
-    ps, _ = model._structs()
-    desc, sh = model._rank_all_desc(B, Q, ur.shape[1], index.shape3)
-    P = index.shape3[0]
-    k, C = int(topk), (_lib.PS_RTM_SEQ_NO_LIST if cand is None else int(cand.shape[1]))
-    dev = qw.device
-    nbytes = lib.ps_rtm_rank_seq_scratch_bytes(desc, sh, C, k, int(slots_per_pass or 0))
-    if nbytes < 0:
-        raise RuntimeError("rank_seq_rtm: %s" % lib.ps_last_error().decode('utf-8', 'replace'))
-    # exactly nbytes, as rank_all_rtm: the C entry sizes its passes from the scratch it is given
-    scratch = model.__dict__.get('_rtm_rank_seq_scratch')
-    if scratch is None or scratch.numel() != nbytes or scratch.device != dev:
-        scratch = model.__dict__['_rtm_rank_seq_scratch'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    tl = _lib.PsRtmSeqTimeline(index.ptr.data_ptr(), index.rids.data_ptr(), index.times.data_ptr(), index.rids.numel())
-    top_idx = torch.empty(B, k, dtype=torch.int64, device=dev)
-    top_score = torch.empty(B, k, dtype=torch.float32, device=dev)
-    rank = torch.empty(B, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, P if cand is None else C, dtype=torch.float32, device=dev) if return_scores else None
-    _lib.check(lib.ps_rtm_rank_seq(desc, sh, ps, index.index.data_ptr(), tl, qw.data_ptr(), ur.data_ptr(), stamps.data_ptr(),
-                                   _lib.ptr(cand), max(C, 0), target.data_ptr(), k, top_idx.data_ptr(), top_score.data_ptr(),
-                                   rank.data_ptr(), _lib.ptr(scores), scratch.data_ptr(), scratch.numel(),
-                                   torch.cuda.current_stream(dev).cuda_stream), 'ps_rtm_rank_seq')
-    return (top_idx, top_score, rank, scores) if return_scores else (top_idx, top_score, rank)
+    def launch(lib, head, qw, ur, target, tail, stamps, cand):
+        tl = _lib.PsRtmSeqTimeline(index.ptr.data_ptr(), index.rids.data_ptr(), index.times.data_ptr(), index.rids.numel())
+        _lib.check(lib.ps_rtm_rank_seq(*head, tl, qw, ur, stamps.data_ptr(), _lib.ptr(cand), 0 if cand is None else cand.shape[1],
+                                       target, *tail), 'ps_rtm_rank_seq')
+    return _rank_rtm(
+        'rank_seq_rtm', model, index, batch, topk, return_scores, '_rtm_rank_seq_scratch',
+        (('time_stamps', 1, True), ('candi_prod_idxs', 2, False)),
+        "u_ridxs must be [B, U], target_prod_idxs and time_stamps [B], candi_prod_idxs [B, C]",
+        lambda lib, desc, sh, k, stamps, cand: lib.ps_rtm_rank_seq_scratch_bytes(
+            desc, sh, _lib.PS_RTM_SEQ_NO_LIST if cand is None else cand.shape[1], k, int(slots_per_pass or 0)),
+        launch, lambda stamps, cand: index.shape3[0] if cand is None else cand.shape[1], timeline=True)
 
 
 def calc_metrics(rank, cutoff=100):

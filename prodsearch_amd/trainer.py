@@ -185,67 +185,63 @@ class Trainer(object):
         ts, ti = sc.topk(min(topk, sc.shape[1]), dim=1)
         return rank, ids.gather(1, ti), ts, users[::seg], queries[::seg]
 
-    def _scores_rank_all_rtm(self, args, global_data, dataset, topk):
-        """``args.rtm_rank_all``: the review transformer over all products in one pass per batch of entries
-        (``evaluate.rank_all_rtm``) instead of ``model.test`` over chunks of ``candi_batch_size`` candidates."""
+    def _scores_rank_rtm(self, args, global_data, dataset, topk, build_index, batches, rank_fn, widen):
+        """The loop of the three one-pass rankers: ``build_index(loader, review_u_p)`` once, ``rank_fn`` per batch of
+        ``batches(loader)``; ``widen``: the ranks as int64, as ``_scores_candidates`` returns them."""
         loader = self.ExpDataloader(args, dataset, batch_size=args.valid_batch_size, shuffle=False, device=args.device)
         tops, scores, ranks, users, queries = [], [], [], [], []
         self.model.eval()
         with torch.no_grad():
             up = global_data.review_u_p if (args.use_user_emb or args.use_item_emb) else None
-            index = self.model.catalogue_index(loader.catalogue_reviews(), up)
-            for b in loader.rank_batches():
-                ti, ts, rk = evaluate.rank_all_rtm(self.model, index, b, topk)
-                tops.append(ti); scores.append(ts); ranks.append(rk)
+            index = build_index(loader, up)
+            for b in batches(loader):
+                ti, ts, rk = rank_fn(self.model, index, b, topk)
+                tops.append(ti); scores.append(ts); ranks.append(rk.to(torch.int64) if widen else rk)
                 users += list(b.user_idxs); queries += list(b.query_idxs)
             self.model.clear_review_embbeddings()
         return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
 
+    def _catalogue_index(self, loader, up):
+        return self.model.catalogue_index(loader.catalogue_reviews(), up)
+
+    def _scores_rank_all_rtm(self, args, global_data, dataset, topk):
+        """``args.rtm_rank_all``: the review transformer over all products in one pass per batch of entries
+        (``evaluate.rank_all_rtm``) instead of ``model.test`` over chunks of ``candi_batch_size`` candidates."""
+        return self._scores_rank_rtm(args, global_data, dataset, topk, self._catalogue_index,
+                                     lambda loader: loader.rank_batches(), evaluate.rank_all_rtm, False)
+
     def _scores_rank_cand_rtm(self, args, global_data, dataset, topk):
         """``args.rtm_rank_all`` with candidate lists: every entry's own list in one pass per batch of entries
         (``evaluate.rank_candidates_rtm``); returns what ``_scores_candidates(..., topk=topk)`` returns."""
-        loader = self.ExpDataloader(args, dataset, batch_size=args.valid_batch_size, shuffle=False, device=args.device)
-        tops, scores, ranks, users, queries = [], [], [], [], []
-        self.model.eval()
-        with torch.no_grad():
-            up = global_data.review_u_p if (args.use_user_emb or args.use_item_emb) else None
-            index = self.model.catalogue_index(loader.catalogue_reviews(), up)
-            for b in loader.candidate_batches():
-                ti, ts, rk = evaluate.rank_candidates_rtm(self.model, index, b, topk)
-                tops.append(ti); scores.append(ts); ranks.append(rk.to(torch.int64))
-                users += list(b.user_idxs); queries += list(b.query_idxs)
-            self.model.clear_review_embbeddings()
-        return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
+        return self._scores_rank_rtm(args, global_data, dataset, topk, self._catalogue_index,
+                                     lambda loader: loader.candidate_batches(), evaluate.rank_candidates_rtm, True)
 
     def _scores_rank_seq_rtm(self, args, global_data, dataset, topk, lists):
         """``args.rtm_rank_all`` in the time-ordered mode (``do_seq_review_test`` without ``train_review_only``): one pass per
         batch of entries over their own candidate lists (``lists``) or over all products (``evaluate.rank_seq_rtm``); returns
         what ``_scores_rank_cand_rtm`` / ``_scores_rank_all_rtm`` return."""
-        loader = self.ExpDataloader(args, dataset, batch_size=args.valid_batch_size, shuffle=False, device=args.device)
-        tops, scores, ranks, users, queries = [], [], [], [], []
-        self.model.eval()
-        with torch.no_grad():
-            up = global_data.review_u_p if (args.use_user_emb or args.use_item_emb) else None
-            index = self.model.timeline_index(*loader.timeline(), review_u_p=up)
-            for b in (loader.seq_candidate_batches() if lists else loader.seq_rank_batches()):
-                ti, ts, rk = evaluate.rank_seq_rtm(self.model, index, b, topk)
-                tops.append(ti); scores.append(ts); ranks.append(rk.to(torch.int64) if lists else rk)
-                users += list(b.user_idxs); queries += list(b.query_idxs)
-            self.model.clear_review_embbeddings()
-        return torch.cat(ranks), torch.cat(tops), torch.cat(scores), users, queries
+        return self._scores_rank_rtm(
+            args, global_data, dataset, topk, lambda loader, up: self.model.timeline_index(*loader.timeline(), review_u_p=up),
+            lambda loader: loader.seq_candidate_batches() if lists else loader.seq_rank_batches(), evaluate.rank_seq_rtm, lists)
 
     @staticmethod
     def _time_ordered(args):
         return bool(getattr(args, 'do_seq_review_test', False)) and not args.train_review_only
 
+    def _scores_one_pass(self, args, global_data, dataset, candi_size, topk):
+        """The route of ``args.rtm_rank_all``: the time-ordered ranker, the whole catalogue (``candi_size`` < 1) or the
+        entries' candidate lists.  ``topk``: of the columns scored, at most 256."""
+        lists = candi_size >= 1
+        topk = min(topk, candi_size if lists else global_data.product_size, 256)
+        if self._time_ordered(args):
+            return self._scores_rank_seq_rtm(args, global_data, dataset, topk, lists)
+        if lists:
+            return self._scores_rank_cand_rtm(args, global_data, dataset, topk)
+        return self._scores_rank_all_rtm(args, global_data, dataset, topk)
+
     def validate(self, args, global_data, valid_dataset):
-        if self.rtm and getattr(args, 'rtm_rank_all', False) and self._time_ordered(args):
-            return evaluate.calc_metrics(self._scores_rank_seq_rtm(args, global_data, valid_dataset, 1,
-                                                                   args.valid_candi_size >= 1)[0], 100)
-        if self.rtm and getattr(args, 'rtm_rank_all', False) and args.valid_candi_size < 1:
-            return evaluate.calc_metrics(self._scores_rank_all_rtm(args, global_data, valid_dataset, 1)[0], 100)
         if self.rtm and getattr(args, 'rtm_rank_all', False):
-            return evaluate.calc_metrics(self._scores_rank_cand_rtm(args, global_data, valid_dataset, 1)[0], 100)
+            return evaluate.calc_metrics(self._scores_one_pass(args, global_data, valid_dataset, args.valid_candi_size, 1)[0], 100)
         if self.rtm:
             size = args.valid_candi_size if args.valid_candi_size >= 1 else global_data.product_size   # trainer.py:127-129
             return evaluate.calc_metrics(self._scores_candidates(args, valid_dataset, size), 100)
@@ -258,16 +254,8 @@ class Trainer(object):
 
     def test(self, args, global_data, test_prod_data, rankfname="test.best_model.ranklist", cutoff=100):
         dataset = self.ExpDataset(args, global_data, test_prod_data)
-        if self.rtm and getattr(args, 'rtm_rank_all', False) and self._time_ordered(args):
-            lists = args.test_candi_size >= 1
-            rank, top_idx, top_score, users, queries = self._scores_rank_seq_rtm(
-                args, global_data, dataset, min(cutoff, args.test_candi_size if lists else global_data.product_size, 256), lists)
-        elif self.rtm and getattr(args, 'rtm_rank_all', False) and args.test_candi_size < 1:
-            rank, top_idx, top_score, users, queries = self._scores_rank_all_rtm(
-                args, global_data, dataset, min(cutoff, global_data.product_size, 256))
-        elif self.rtm and getattr(args, 'rtm_rank_all', False):
-            rank, top_idx, top_score, users, queries = self._scores_rank_cand_rtm(
-                args, global_data, dataset, min(cutoff, args.test_candi_size, 256))
+        if self.rtm and getattr(args, 'rtm_rank_all', False):
+            rank, top_idx, top_score, users, queries = self._scores_one_pass(args, global_data, dataset, args.test_candi_size, cutoff)
         elif self.rtm:
             size = args.test_candi_size if args.test_candi_size >= 1 else global_data.product_size     # trainer.py:141-143
             rank, top_idx, top_score, users, queries = self._scores_candidates(args, dataset, size, topk=min(cutoff, size))

@@ -6,11 +6,11 @@ The shape is validation's: C4 (d = 128, 8 heads, ff 512, one layer, 20 + 30 revi
 B = 24 entries, C = 500 candidates per entry — 499 drawn without replacement from a Zipf-like product distribution plus the
 target, as ``ProdSearchDataset`` draws them for ``--valid_candi_size 500``.  Two forms of one validation batch are timed:
 
-    one_pass   rank_candidates_rtm: entry side once, candidate kernel -> per-pair tail -> head, selection on the device
+    one_pass   rank_candidates_rtm: entry side once, rr_slot_kernel -> per-pair tail -> head, selection on the device
     chunked    what Trainer._scores_candidates does: one model.test() call on the assembled chunk + its torch ranking chain
 
 Boxes of one pool differ by several per cent, so only figures of one process are compared; the two forms alternate.  The
-candidate kernel's and the fused tail's durations come from the kernel timer's bound event pairs (``ps_ktimer_arm``), a run
+slot kernel's (stage ``rtm_rank_cand``) and the fused tail's durations come from the kernel timer's bound event pairs (``ps_ktimer_arm``), a run
 each.  One JSON line per form and round, then the medians.
 
     python tools/bench_rtm_cand.py [--steps 20] [--warmup 3] [--rounds 5] [--products 10000] [--entries 24] [--cands 500]
@@ -138,7 +138,7 @@ def main():
           % (o.rounds, o.steps, P, B, Cw, U, I, d, R.H, R.RC, o.topk))
     print('one_pass  %9.3f ms/batch (min %.3f, max %.3f)' % (one, min(res['one_pass']), max(res['one_pass'])))
     print('chunked   %9.3f ms/batch (min %.3f, max %.3f)   ratio %.2fx' % (chk, min(res['chunked']), max(res['chunked']), chk / one))
-    print('candidate kernel %.1f us x %d: %.2f ns per pair over %d pairs (rr_pair_kernel: 76 us per 32,760 pairs = 2.32 ns); '
+    print('rr_slot_kernel (static lists) %.1f us x %d: %.2f ns per pair over %d pairs (rr_pair_kernel: 76 us per 32,760 pairs = 2.32 ns); '
           '%d review rows, %.1f MB of K / V rows -> %.2f TB/s'
           % (cand_us, n_cand, 1e3 * cand_us / pairs, pairs, rows, row_bytes / 1e6, row_bytes / max(1e-9, cand_us) / 1e6))
     print('fused tail %.1f us x %d -> tail share of the two %.1f %%, of the batch %.1f %%'

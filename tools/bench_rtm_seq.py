@@ -12,8 +12,8 @@ of one batch are timed:
     seq_cat       rank_seq_rtm over the catalogue             chunked_cat    20 model.test() calls of 500 + ranking chain
 
 Boxes of one pool differ by several per cent, so only figures of one process are compared; the forms alternate.  The cost of
-the search and the window: ``rr_seq_kernel`` with every stamp at INT64_MAX reads exactly the rows ``rr_cand_kernel`` reads from
-the static catalogue of every item's last 30 reviews, so the two kernels' times (the kernel timer's bound event pairs, a run
+the search and the window: ``rr_slot_kernel<EPL, true>`` with every stamp at INT64_MAX reads exactly the rows its static form
+(``<EPL, false>``) reads from the static catalogue of every item's last 30 reviews, so the two kernels' times (the kernel timer's bound event pairs, a run
 each) differ by the lookup alone.  One JSON line per form and round, then the medians.
 
     python tools/bench_rtm_seq.py [--steps 20] [--warmup 3] [--rounds 5] [--products 10000] [--entries 24] [--cands 500]
@@ -166,7 +166,7 @@ def main():
     # ... and with every stamp at INT64_MAX the time-ordered kernel gives the static kernel's bits
     s_max = evaluate.rank_seq_rtm(m, index, b_list_max, o.topk, return_scores=True)[3]
     s_st = evaluate.rank_candidates_rtm(m, st_index, st_listed, o.topk, return_scores=True)[3]
-    print(json.dumps(dict(check='rr_seq_kernel at INT64_MAX vs rr_cand_kernel', equal_bits=bool(torch.equal(s_max, s_st)))), flush=True)
+    print(json.dumps(dict(check='rr_slot_kernel: time-ordered at INT64_MAX vs static', equal_bits=bool(torch.equal(s_max, s_st)))), flush=True)
     assert torch.equal(s_max, s_st)
     for f in forms.values():
         R.timed(f, o.warmup)
@@ -197,13 +197,13 @@ def main():
             print('%-12s %9.3f ms/batch (min %.3f, max %.3f)   ratio %.2fx' % (b, med[b], min(res[b]), max(res[b]), med[b] / med[a]))
             assert min(res[b]) > max(res[a]), "the one-pass form must be faster by more than the spread of the rounds"
             out.update({a + '_ms': med[a], b + '_ms': med[b], a + '_ratio': med[b] / med[a]})
-    print('rr_seq_kernel %.1f us per %d pairs = %.2f ns per pair (the entries\' own stamps, %d review rows)'
+    print('rr_slot_kernel (time-ordered) %.1f us per %d pairs = %.2f ns per pair (the entries\' own stamps, %d review rows)'
           % (seq_us, pairs, 1e3 * seq_us / pairs, rows_list))
-    print('same rows: rr_seq_kernel at INT64_MAX %.1f us = %.2f ns per pair, rr_cand_kernel on the static catalogue %.1f us = %.2f ns '
+    print('same rows: time-ordered at INT64_MAX %.1f us = %.2f ns per pair, the static form on the static catalogue %.1f us = %.2f ns '
           'per pair -> the search and the window cost %.1f us, %.2f ns per pair'
           % (seq_max_us, 1e3 * seq_max_us / pairs, cand_us, 1e3 * cand_us / pairs, seq_max_us - cand_us, 1e3 * (seq_max_us - cand_us) / pairs))
     n_cat //= o.steps
-    print('catalogue form: rr_seq_kernel %.1f us x %d passes = %.2f ns per pair over %d pairs'
+    print('catalogue form: rr_slot_kernel (time-ordered) %.1f us x %d passes = %.2f ns per pair over %d pairs'
           % (cat_us, n_cat, 1e3 * cat_us * n_cat / (B * P), B * P))
     out.update(seq_us=seq_us, seq_max_us=seq_max_us, cand_us=cand_us, cat_us=cat_us, cat_passes=n_cat)
     print(json.dumps(out))
