@@ -654,6 +654,24 @@ int ps_gemm_f32(const float* A, int lda, int ta, const float* Bm, int ldb, int t
                 float* Cm, int ldc, int M, int N, int K, const float* bias, float alpha,
                 int accumulate, ps_stream_t stream);
 
+/* ------------------------------------------------------------------ several tables in one coalesce
+ * A model with several row-sparse tables (the review transformer: review / user / item / word) builds all its touched lists
+ * in THREE launches instead of three per table.  Each entry is what one ps_coalesce_rows call takes — 1..8 index lists,
+ * n_rows, pad_row, the table's own workspace (ps_coalesce_ws_bytes, zeroed once, left zeroed), rows_out / cap / count_out —
+ * and gets what that call gives: the sorted unique non-pad ids, bit for bit, and the same status word (ps_coalesce_bad_flag:
+ * 1 an id outside [0, n_rows) was dropped, 2 more unique rows than cap), set for that table only.  n_tabs 1..4. */
+typedef struct PsCoalesceTable {
+  PsIdxList lists[8];
+  int32_t n_lists;
+  int32_t pad_;
+  int64_t n_rows, pad_row;
+  void* ws_dev;
+  int64_t* rows_out_dev;
+  int64_t cap;
+  int32_t* count_out_dev;
+} PsCoalesceTable;
+int ps_coalesce_tables(const PsCoalesceTable* tabs_host, int32_t n_tabs, ps_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

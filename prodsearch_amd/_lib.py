@@ -69,6 +69,15 @@ class PsIdxList(C.Structure):
     _fields_ = [('idx', C.c_void_p), ('n', C.c_int64)]
 
 
+PS_MAX_IDX_LISTS, PS_MAX_COALESCE_TABLES = 8, 4
+
+
+class PsCoalesceTable(C.Structure):
+    _fields_ = [('lists', PsIdxList * PS_MAX_IDX_LISTS), ('n_lists', C.c_int32), ('pad_', C.c_int32),
+                ('n_rows', C.c_int64), ('pad_row', C.c_int64), ('ws_dev', C.c_void_p), ('rows_out_dev', C.c_void_p),
+                ('cap', C.c_int64), ('count_out_dev', C.c_void_p)]
+
+
 class PsRowTable(C.Structure):
     _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p),
                 ('rows', C.c_void_p), ('count', C.c_void_p), ('cap', C.c_int64), ('d', C.c_int32),
@@ -229,6 +238,7 @@ SYMBOLS = {
     'ps_coalesce_ws_bytes': (C.c_int64, [C.c_int64]),
     'ps_coalesce_rows': (C.c_int, [C.POINTER(PsIdxList), C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'ps_coalesce_tables': (C.c_int, [C.POINTER(PsCoalesceTable), C.c_int32, C.c_void_p]),
     'ps_gather_rows': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'ps_scatter_rows': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'ps_zero_rows': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

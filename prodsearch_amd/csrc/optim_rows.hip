@@ -146,6 +146,151 @@ extern "C" int ps_coalesce_rows(const PsIdxList* lists_host, int32_t n_lists, in
   return PS_OK;
 }
 
+// ---------------------------------------------------------------- several tables in one coalesce (ps_coalesce_tables)
+// A model with T row-sparse tables would pay 3 T launches for its touched lists.  Here the three kernels run ONCE: the mark
+// grid is the concatenation of the tables' index spaces (each rounded up to whole blocks), the count / emit grids the
+// concatenation of their bitmap blocks; a block finds its table in a prefix array of at most four entries that travels
+// by value.  Per table the workspace layout, the status word and the output are ps_coalesce_rows' own.
+#define CO_MAX_TABLES 4
+struct CoTab {
+  IdxLists L;
+  int64_t n_rows, pad_row, n_words;
+  unsigned long long* bitmap; int32_t* blocksum; int32_t* bad;
+  int64_t* rows; int64_t cap; int32_t* count;
+};
+struct CoTabs { CoTab t[CO_MAX_TABLES]; int32_t mblk0[CO_MAX_TABLES + 1]; int32_t blk0[CO_MAX_TABLES + 1]; int32_t n; };
+
+__device__ inline int co_find(const int32_t* blk0, int n, int blk) {
+  int k = 0;
+  while (k < n - 1 && blk >= blk0[k + 1]) ++k;
+  return k;
+}
+
+__global__ __launch_bounds__(256) void co_mark_tabs_kernel(CoTabs T) {
+  const int t = co_find(T.mblk0, T.n, (int)blockIdx.x);
+  const CoTab& tb = T.t[t];
+  // (a table with blocks here has total > 0.)  The id is loaded first, from a clamped position, and judged afterwards: no
+  // load sits behind the bounds test
+  const int64_t i0 = (int64_t)((int)blockIdx.x - T.mblk0[t]) * 256 + threadIdx.x;
+  int64_t i = i0 < tb.L.total ? i0 : tb.L.total - 1;
+  int k = 0;
+  while (k < tb.L.n - 1 && i >= tb.L.l[k].n) { i -= tb.L.l[k].n; ++k; }
+  const int64_t r = tb.L.l[k].idx[i];
+  const bool live = i0 < tb.L.total && r != tb.pad_row;
+  const bool in = r >= 0 && r < tb.n_rows;
+  const int64_t rr = in ? r : 0;
+  const unsigned long long bit = 1ull << (rr & 63);
+  const unsigned long long seen = __builtin_nontemporal_load(&tb.bitmap[rr >> 6]);
+  if (!live) return;
+  if (!in) { *tb.bad = 1; return; }
+  if (!(seen & bit)) atomicOr(&tb.bitmap[rr >> 6], bit);      // popular rows repeat: no atomic once the bit is visible
+}
+
+__global__ __launch_bounds__(256) void co_count_tabs_kernel(CoTabs T) {
+  __shared__ int sh[4];
+  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const CoTab& tb = T.t[t];
+  const int lb = (int)blockIdx.x - T.blk0[t];
+  const int64_t w0 = (int64_t)lb * CO_WORDS_PER_BLOCK + threadIdx.x;
+  const unsigned long long w = tb.bitmap[w0 < tb.n_words ? w0 : tb.n_words - 1];
+  int c = w0 < tb.n_words ? __popcll(w) : 0;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) tb.blocksum[lb] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(256) void co_emit_tabs_kernel(CoTabs T) {
+  __shared__ int sh[256];
+  __shared__ int base_sh;
+  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const CoTab& tb = T.t[t];
+  const int lb = (int)blockIdx.x - T.blk0[t];
+  const int nb = T.blk0[t + 1] - T.blk0[t];
+  const int64_t w0 = (int64_t)lb * CO_WORDS_PER_BLOCK + threadIdx.x;
+  const unsigned long long w = tb.bitmap[w0 < tb.n_words ? w0 : tb.n_words - 1];
+  // rows emitted by earlier blocks of THIS table
+  sh[threadIdx.x] = strided_sum_i32<4>(tb.blocksum, lb, threadIdx.x, 256);
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) base_sh = sh[0];
+  __syncthreads();
+  const int base = base_sh;
+  __syncthreads();
+  const int c = w0 < tb.n_words ? __popcll(w) : 0;
+  // exclusive scan of c over the block (Hillis-Steele in LDS)
+  sh[threadIdx.x] = c;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    int add = ((int)threadIdx.x >= o) ? sh[threadIdx.x - o] : 0;
+    __syncthreads();
+    sh[threadIdx.x] += add;
+    __syncthreads();
+  }
+  int64_t pos = (int64_t)base + sh[threadIdx.x] - c;
+  if (c) {
+    unsigned long long x = w;
+    while (x) {
+      const int b = __ffsll((long long)x) - 1;
+      x &= x - 1;
+      if (pos < tb.cap) tb.rows[pos] = w0 * 64 + b; else *tb.bad = 2;
+      ++pos;
+    }
+    tb.bitmap[w0] = 0ull;                        // leave the bitmap clean for the next step
+  }
+  if (lb == nb - 1 && threadIdx.x == 255) *tb.count = base + sh[255];
+}
+
+extern "C" int ps_coalesce_tables(const PsCoalesceTable* tabs_host, int32_t n_tabs, ps_stream_t stream) {
+  PS_REQUIRE(tabs_host && n_tabs >= 1 && n_tabs <= CO_MAX_TABLES, "coalesce_tables: 1..%d tables (%d given)", CO_MAX_TABLES,
+             (int)n_tabs);
+  CoTabs T = CoTabs();
+  T.n = n_tabs;
+  int64_t mb = 0, cb = 0, all = 0;
+  for (int t = 0; t < n_tabs; ++t) {
+    const PsCoalesceTable& h = tabs_host[t];
+    CoTab& tb = T.t[t];
+    PS_REQUIRE(h.n_lists > 0 && h.n_lists <= PS_MAX_IDX_LISTS, "coalesce_tables: table %d: 1..%d index lists", t, PS_MAX_IDX_LISTS);
+    PS_REQUIRE(h.n_rows > 0 && h.n_rows < ((int64_t)1 << 37) && h.ws_dev && h.rows_out_dev && h.count_out_dev && h.cap > 0,
+               "coalesce_tables: table %d: bad argument", t);
+    for (int u = 0; u < t; ++u)
+      PS_REQUIRE(tabs_host[u].ws_dev != h.ws_dev, "coalesce_tables: tables %d and %d share a workspace", u, t);
+    tb.L.n = h.n_lists; tb.L.total = 0;
+    for (int i = 0; i < h.n_lists; ++i) {
+      PS_REQUIRE(h.lists[i].n >= 0 && (h.lists[i].n == 0 || h.lists[i].idx), "coalesce_tables: table %d: list %d null", t, i);
+      tb.L.l[i] = h.lists[i];
+      tb.L.total += h.lists[i].n;
+    }
+    const int64_t need = tb.L.total < h.n_rows ? tb.L.total : h.n_rows;
+    PS_REQUIRE(h.cap >= need, "coalesce_tables: table %d: rows_out capacity %lld < %lld", t, (long long)h.cap, (long long)need);
+    all += tb.L.total;
+    PS_REQUIRE(all < ((int64_t)1 << 31), "coalesce_tables: too many indices");
+    tb.n_rows = h.n_rows; tb.pad_row = h.pad_row; tb.n_words = co_words(h.n_rows);
+    tb.bitmap = (unsigned long long*)h.ws_dev;
+    tb.blocksum = (int32_t*)(tb.bitmap + tb.n_words);
+    tb.bad = tb.blocksum + co_blocks(h.n_rows);
+    tb.rows = h.rows_out_dev; tb.cap = h.cap; tb.count = h.count_out_dev;
+    T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb;
+    mb += (tb.L.total + 255) / 256;
+    cb += co_blocks(h.n_rows);
+    PS_REQUIRE(mb < ((int64_t)1 << 31) && cb < ((int64_t)1 << 31), "coalesce_tables: grid too large");
+  }
+  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) { T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb; }
+  hipStream_t st = (hipStream_t)stream;
+  if (mb > 0) {
+    hipLaunchKernelGGL(co_mark_tabs_kernel, dim3((unsigned)mb), dim3(256), 0, st, T);
+    PS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(co_count_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T);
+  PS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(co_emit_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
 // ---------------------------------------------------------------- gather / scatter of touched rows
 // 32 lanes per row, 16 B per lane; 8 rows per 256-thread block.
 template <int MODE>   // 0: vals = tab[rows]   1: tab[rows] = vals

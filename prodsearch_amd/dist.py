@@ -225,6 +225,9 @@ def _refuse_frozen_words(model):
         raise NotImplementedError("data-parallel training with a frozen word table (pretrain_emb_dir) is not supported")
     # the review transformer's other tables (pretrain_emb_dir's doc_emb, fix_emb, pretrain_up_emb_dir): same refusal
     tabs = getattr(model, '_hot_tables', None)
+    if tabs is not None and getattr(model, '_row_sparse', lambda: False)():
+        # the review transformer's touched lists have no row exchange yet (SparseGradExchange serves the item models)
+        raise NotImplementedError("data-parallel training of the review transformer with row_sparse_adam is not supported")
     for name, p in (tabs() if tabs is not None else {}).items():
         if not p.requires_grad:
             raise NotImplementedError("data-parallel training with a frozen %s table (pretrain_emb_dir / "

@@ -7,7 +7,11 @@ from it.  What it owns is the protocol ``dist.py``, ``optimizers.py``, ``sharded
     buffer ``_grad_flat`` with a view per graded parameter (``_grad_views``), laid out by :func:`flat_layout`;
   * ``_regrade()``: the rebuild of that layout when a table's ``requires_grad`` flips between steps;
   * the loss tensor whose plain ``backward()`` is one C-ABI call (``_loss_forward``), ``_assign_grads`` and the dense
-    ``_zero_for_backward``, the per-shape ``_Plan`` cache, the alias tables of the word sampler.
+    ``_zero_for_backward``, the per-shape ``_Plan`` cache, the alias tables of the word sampler;
+  * the row-sparse optimizer's host side (``args.row_sparse_adam``): the touched-row lists of a step's index tensors
+    (``_coalesce_touched`` -> ``p._ps_rows``, which ``Optimizer._build_plan`` looks for), ``touched_rows``,
+    ``check_index_errors``, the zeroing of rows a backward left dirty and the refusal to accumulate over them.  A model names
+    its tables and lists in ``_row_sparse`` / ``_sparse_paths`` / ``_index_lists``.
 
 A model supplies the hooks listed under "hooks" below.  This module imports neither model and runs no device code on import.
 """
@@ -69,7 +73,7 @@ class _LossTensor(torch.Tensor):
 class _Plan(object):
     """Per-shape cached call state: descriptor, batch struct, workspace (+ what each model parks beside them)."""
     __slots__ = ('desc', 'batch', 'ws', 'layout', 'key', 'neg_items', 'neg_words', 'dummy_items', 'keep', 'staged',
-                 'coalesced_at')
+                 'coalesced_at', 'lists')
     __getitem__ = lambda self, slot: getattr(self, slot)     # the review model's plans were dicts: plan['desc'] still reads
 
 
@@ -123,8 +127,22 @@ class HotPathModule(nn.Module):
         return None
 
     def _grad_order(self, path, p):
-        """Sort key of a graded parameter in the flat buffer (the sort is stable)."""
-        return p.numel()
+        """Sort key of a graded parameter in the flat buffer (the sort is stable): by size, the row-sparse tables behind
+        everything dense."""
+        return (path in self._sparse_paths(), p.numel())
+
+    def _row_sparse(self):
+        """``args.row_sparse_adam`` as this model takes it: table gradients stay dense tensors, but zeroing / clip / Adam
+        only visit the rows a step touched."""
+        return False
+
+    def _sparse_paths(self):
+        """Paths of the tables handled by their touched-row lists (empty unless ``_row_sparse()``)."""
+        return ()
+
+    def _index_lists(self, path, plan):
+        """([index tensors of the step that address ``path``'s rows], that table's pad row)."""
+        raise NotImplementedError
 
     def _fill_extra(self, ps):
         """Fields of the parameter struct that are not parameters."""
@@ -207,7 +225,13 @@ class HotPathModule(nn.Module):
             v = self._grad_flat[o:o + p.numel()].view_as(p)
             self._grad_views.append((p, v))
             self._set_field(gs, path, v.data_ptr())
-        self._structs_built([(path, p, v) for (path, p), (_, v) in zip(graded, self._grad_views)])
+        built = [(path, p, v) for (path, p), (_, v) in zip(graded, self._grad_views)]
+        # row-sparse mode: the flat buffer is [dense tensors | row-sparse tables]; only the first part is ever memset,
+        # table rows are re-zeroed by the optimizer (or zero_grad) through their touched list
+        sparse = self._sparse_paths()
+        self._n_dense_grad = sum(slice_floats(p.numel()) for path, p, _ in built if path not in sparse)
+        self._sparse_tabs = [t for t in built if t[0] in sparse]
+        self._structs_built(built)
         self._params_struct, self._grads_struct = ps, gs
         self.__dict__['_grad_key_at'] = self._grad_key()
         return ps, gs
@@ -271,8 +295,108 @@ class HotPathModule(nn.Module):
         return fresh
 
     def _zero_for_backward(self):
-        _lib.check(_lib.load().ps_zero_floats(self._grad_flat.data_ptr(), self._grad_flat.numel(), self._stream()),
-                   'ps_zero_floats')
+        lib = _lib.load()
+        st = self._stream()
+        if not self._row_sparse():
+            _lib.check(lib.ps_zero_floats(self._grad_flat.data_ptr(), self._grad_flat.numel(), st), 'ps_zero_floats')
+            return
+        _lib.check(lib.ps_zero_floats(self._grad_flat.data_ptr(), self._n_dense_grad, st), 'ps_zero_floats')
+        for path, p, gview in self._sparse_tabs:
+            info = getattr(p, '_ps_rows', None)
+            if info is not None and info['dirty']:       # touched by a backward no optimizer step consumed
+                rows, count, cap = self._rows_view(info)
+                _lib.check(lib.ps_zero_rows(gview.data_ptr(), p.shape[1], rows.data_ptr(), count.data_ptr(), cap, st),
+                           'ps_zero_rows')
+                info['dirty'] = False
+
+    # ------------------------------------------------------------ row-sparse optimizer support
+    def _refuse_dirty_accumulation(self):
+        """A second backward onto gradients the first one left (no ``zero_grad()``, no ``optim.step()`` between): its touched
+        lists would replace the first one's, whose rows nobody could find again."""
+        if self._row_sparse() and any(getattr(p, '_ps_rows', {}).get('dirty') for _, p, _ in self._sparse_tabs):
+            raise NotImplementedError("row_sparse_adam: gradient accumulation over several backwards is not "
+                                      "supported; call model.zero_grad() (trainer.py:76) or optim.step() first")
+
+    def _coalesce_touched(self, plan):
+        """The sorted unique non-pad row ids of the step's index lists, per row-sparse table (``p._ps_rows``): one
+        ``ps_coalesce_tables`` call when several tables have lists, ``ps_coalesce_rows`` for a single one."""
+        lib = _lib.load()
+        dev, st = self._dev(), self._stream()
+        work = []
+        for path, p, gview in self._sparse_tabs:
+            lists, pad = self._index_lists(path, plan)
+            info = getattr(p, '_ps_rows', None)
+            total = sum(t.numel() for t in lists)
+            cap = max(1, min(total, p.shape[0]))
+            if info is None or info['rows'].numel() < cap or info['grad_ptr'] != gview.data_ptr():
+                info = dict(rows=torch.empty(cap, device=dev, dtype=torch.int64),
+                            count=torch.zeros(1, device=dev, dtype=torch.int32),
+                            ws=torch.zeros(lib.ps_coalesce_ws_bytes(p.shape[0]), device=dev, dtype=torch.uint8),
+                            grad_ptr=gview.data_ptr(), dirty=False)
+                p._ps_rows = info
+            info['cap'] = cap
+            info['active'] = None          # a data-parallel exchange installs the ranks' union here (dist.SparseGradExchange)
+            if not lists:
+                info['count'].zero_()
+                continue
+            work.append((p, info, lists, pad))
+        if len(work) > 1 and len(work) <= _lib.PS_MAX_COALESCE_TABLES:
+            tabs = (_lib.PsCoalesceTable * len(work))()
+            for t, (p, info, lists, pad) in zip(tabs, work):
+                for i, x in enumerate(lists):
+                    t.lists[i].idx, t.lists[i].n = x.data_ptr(), x.numel()
+                t.n_lists, t.n_rows, t.pad_row = len(lists), p.shape[0], pad
+                t.ws_dev, t.rows_out_dev, t.cap = info['ws'].data_ptr(), info['rows'].data_ptr(), info['rows'].numel()
+                t.count_out_dev = info['count'].data_ptr()
+            _lib.check(lib.ps_coalesce_tables(tabs, len(work), st), 'ps_coalesce_tables')
+        else:
+            for p, info, lists, pad in work:
+                arr = (_lib.PsIdxList * len(lists))()
+                for i, t in enumerate(lists):
+                    arr[i].idx, arr[i].n = t.data_ptr(), t.numel()
+                _lib.check(lib.ps_coalesce_rows(arr, len(lists), p.shape[0], pad, info['ws'].data_ptr(),
+                                                info['rows'].data_ptr(), info['rows'].numel(),
+                                                info['count'].data_ptr(), st), 'ps_coalesce_rows')
+        for _, info, _, _ in work:
+            info['dirty'] = True
+
+    @staticmethod
+    def _rows_view(info):
+        """(rows, count, cap) the optimizer and zero_grad walk: the ranks' union after an exchange, else this rank's."""
+        return info.get('active') or (info['rows'], info['count'], info['cap'])
+
+    def touched_rows(self):
+        """{state_dict key: sorted unique row ids} of the last backward (row-sparse mode; host sync)."""
+        self.check_index_errors()
+        out = {}
+        for name, p in self.named_parameters():
+            info = getattr(p, '_ps_rows', None)
+            if info is not None:
+                rows, count, _ = self._rows_view(info)
+                out[name] = rows[:int(count[0])].clone()
+        return out
+
+    def check_index_errors(self):
+        """Row-sparse mode: raise if a step's index lists held a row outside its table or overflowed a touched list
+        (the kernels drop such rows and set a status word; reading it is a host sync, so the step itself never does —
+        the trainer calls this where it reads the loss)."""
+        if not self._row_sparse():
+            return
+        lib = _lib.load()
+        for name, p in self.named_parameters():
+            info = getattr(p, '_ps_rows', None)
+            if info is None:
+                continue
+            for ws in (info['ws'], (info.get('xchg') or {}).get('ws')):
+                if ws is None:
+                    continue
+                addr = lib.ps_coalesce_bad_flag(ws.data_ptr(), p.shape[0])
+                off = addr - ws.data_ptr()
+                flag = int(ws[off:off + 4].view(torch.int32)[0])
+                if flag:
+                    ws[off:off + 4].zero_()
+                    raise RuntimeError("row-sparse step: %s" % ("an index outside [0, %d) addressed %s" % (p.shape[0], name)
+                                       if flag == 1 else "touched-row list of %s overflowed its capacity" % name))
 
     # --------------------------------------------------------------- test support
     def workspace_view(self, plan, name, shape):

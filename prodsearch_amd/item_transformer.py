@@ -349,15 +349,10 @@ class ItemTransformerRanker(HotPathModule):
             ps.pe = self.transformer_encoder.pos_emb.pe.data_ptr()
 
     def _structs_built(self, graded):
-        sparse = self._sparse_paths()
         self._n_small = sum(slice_floats(p.numel()) for _, p, _ in graded if p.numel() < (1 << 20))
-        # row-sparse mode: the flat buffer is [dense tensors | row-sparse tables]; only the first part is
-        # ever memset, table rows are re-zeroed by the optimizer (or zero_grad) through their touched list
-        self._n_dense_grad = sum(slice_floats(p.numel()) for path, p, _ in graded if path not in sparse)
         # what a data-parallel exchange all-reduces: the small tensors only — with a sharded item table the receive buffer's
         # gradient (the LARGEST of the non-sparse tensors, hence the last of them) travels to the owners instead
         self._n_allreduce_grad = self._n_dense_grad - (slice_floats(self.product_emb.weight.numel()) if self._shard is not None else 0)
-        self._sparse_tabs = [t for t in graded if t[0] in sparse]
         self._loss_acc = torch.zeros(2, device=self._dev(), dtype=torch.float32)
 
     def _regrade_refusal(self):
@@ -625,85 +620,11 @@ class ItemTransformerRanker(HotPathModule):
             return d.B * Lmax if tem else 1
         return d.B * (d.Q + d.W + d.W * d.K)
 
-    def _coalesce_touched(self, plan):
-        lib = _lib.load()
-        dev, st = self._dev(), self._stream()
-        for path, p, gview in self._sparse_tabs:
-            lists, pad = self._index_lists(path, plan)
-            info = getattr(p, '_ps_rows', None)
-            total = sum(t.numel() for t in lists)
-            cap = max(1, min(total, p.shape[0]))
-            if info is None or info['rows'].numel() < cap or info['grad_ptr'] != gview.data_ptr():
-                info = dict(rows=torch.empty(cap, device=dev, dtype=torch.int64),
-                            count=torch.zeros(1, device=dev, dtype=torch.int32),
-                            ws=torch.zeros(lib.ps_coalesce_ws_bytes(p.shape[0]), device=dev, dtype=torch.uint8),
-                            grad_ptr=gview.data_ptr(), dirty=False)
-                p._ps_rows = info
-            info['cap'] = cap
-            info['active'] = None          # a data-parallel exchange installs the ranks' union here (dist.SparseGradExchange)
-            if not lists:
-                info['count'].zero_()
-                continue
-            arr = (_lib.PsIdxList * len(lists))()
-            for i, t in enumerate(lists):
-                arr[i].idx, arr[i].n = t.data_ptr(), t.numel()
-            _lib.check(lib.ps_coalesce_rows(arr, len(lists), p.shape[0], pad, info['ws'].data_ptr(),
-                                            info['rows'].data_ptr(), info['rows'].numel(),
-                                            info['count'].data_ptr(), st), 'ps_coalesce_rows')
-            info['dirty'] = True
-
-    @staticmethod
-    def _rows_view(info):
-        """(rows, count, cap) the optimizer and zero_grad walk: the ranks' union after an exchange, else this rank's."""
-        return info.get('active') or (info['rows'], info['count'], info['cap'])
-
-    def touched_rows(self):
-        """{state_dict key: sorted unique row ids} of the last backward (row-sparse mode; host sync)."""
-        self.check_index_errors()
-        out = {}
-        for name, p in self.named_parameters():
-            info = getattr(p, '_ps_rows', None)
-            if info is not None:
-                rows, count, _ = self._rows_view(info)
-                out[name] = rows[:int(count[0])].clone()
-        return out
-
     def check_index_errors(self):
-        """Row-sparse mode: raise if a step's index lists held a row outside its table or overflowed a touched list
-        (the kernels drop such rows and set a status word; reading it is a host sync, so the step itself never does —
-        the trainer calls this where it reads the loss)."""
-        import ctypes
-        lib = _lib.load()
+        """``HotPathModule.check_index_errors``, and the status word of a row-sharded item table's requests."""
         if self.__dict__.get('_shard') is not None:
             self._shard.check_errors()
-        for name, p in self.named_parameters():
-            info = getattr(p, '_ps_rows', None)
-            if info is None:
-                continue
-            for ws in (info['ws'], (info.get('xchg') or {}).get('ws')):
-                if ws is None:
-                    continue
-                addr = lib.ps_coalesce_bad_flag(ws.data_ptr(), p.shape[0])
-                off = addr - ws.data_ptr()
-                flag = int(ws[off:off + 4].view(torch.int32)[0])
-                if flag:
-                    ws[off:off + 4].zero_()
-                    raise RuntimeError("row-sparse step: %s" % ("an index outside [0, %d) addressed %s" % (p.shape[0], name)
-                                       if flag == 1 else "touched-row list of %s overflowed its capacity" % name))
-
-    def _zero_for_backward(self):
-        if not self._row_sparse():
-            return super()._zero_for_backward()
-        lib = _lib.load()
-        st = self._stream()
-        _lib.check(lib.ps_zero_floats(self._grad_flat.data_ptr(), self._n_dense_grad, st), 'ps_zero_floats')
-        for path, p, gview in self._sparse_tabs:
-            info = getattr(p, '_ps_rows', None)
-            if info is not None and info['dirty']:       # touched by a backward no optimizer step consumed
-                rows, count, cap = self._rows_view(info)
-                _lib.check(lib.ps_zero_rows(gview.data_ptr(), p.shape[1], rows.data_ptr(), count.data_ptr(), cap, st),
-                           'ps_zero_rows')
-                info['dirty'] = False
+        super().check_index_errors()
 
     def zero_grad(self, set_to_none=True):
         """``model.zero_grad()`` (trainer.py:76).  nn.Module's version walks the module tree on every call (≈120 us of
@@ -735,9 +656,8 @@ class ItemTransformerRanker(HotPathModule):
         if self._assign_grads():
             if not self.__dict__.get('_grad_clean', False):     # (clean: the last optimizer step left the buffer at 0)
                 self._zero_for_backward()
-        elif self._row_sparse() and any(getattr(p, '_ps_rows', {}).get('dirty') for _, p, _ in self._sparse_tabs):
-            raise NotImplementedError("row_sparse_adam: gradient accumulation over several backwards is not "
-                                      "supported; call model.zero_grad() (trainer.py:76) or optim.step() first")
+        else:
+            self._refuse_dirty_accumulation()
         pre = self._row_sparse() and getattr(plan, 'coalesced_at', None) == self._fwd_step     # lazy_exact_adam: done before the forward
         if self._row_sparse() and not pre:
             # the touched lists only need the step's indices: built on a side stream under the backward

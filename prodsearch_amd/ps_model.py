@@ -410,6 +410,39 @@ class ProductRanker(HotPathModule):
         the rebuilt gradient struct, and ``ps_rtm_backward`` refuses the pair (its frozen_mask message) before launching
         anything."""
         self._plans = {}
+        for p in self._hot_tables().values():        # touched lists belong to the old gradient layout
+            if getattr(p, '_ps_rows', None) is not None:
+                del p._ps_rows
+
+    # ------------------------------------------------------------ row-sparse optimizer support
+    def _row_sparse(self):
+        """``args.row_sparse_adam``: the trainable tables below are zeroed, clipped and updated by the rows a step touched
+        (untouched rows keep p, m, v: DESIGN.md §5b).  With ``args.lazy_exact_adam`` — the dense optimizer's results, which
+        this model has no replay for — the model stays on the dense path, which IS that result."""
+        a = self.args
+        return bool(getattr(a, 'row_sparse_adam', False)) and not bool(getattr(a, 'lazy_exact_adam', False))
+
+    def _sparse_paths(self):
+        """The trainable id-addressed tables: review (pv) / user / item, and the word table under the pv encoder only — the
+        word-mean encoders address ~16 word slots per vocabulary row a step, which is not sparse."""
+        if not self._row_sparse():
+            return ()
+        tabs = self._hot_tables()
+        names = ('review_emb', 'user_emb', 'product_emb') + (('word_emb',) if self.review_encoder_name == 'pv' else ())
+        return tuple((n,) for n in names if n in tabs and tabs[n].requires_grad)
+
+    def _index_lists(self, path, plan):
+        ls = plan.lists
+        if path == ('review_emb',):
+            return [ls['pos_prod_ridxs'], ls['neg_prod_ridxs']], self.review_pad_idx
+        if path == ('user_emb',):
+            return [ls['pos_user_idxs'], ls['neg_user_idxs']], self.user_pad_idx
+        if path == ('product_emb',):
+            return [ls['pos_item_idxs'], ls['neg_item_idxs']], self.prod_pad_idx
+        words = [ls['query_word_idxs']]
+        if plan.desc.train_pv:                       # the PV loss: each positive review's window words and their draws
+            words += [ls['pos_prod_rword_idxs'], ls['neg_word_idxs']]
+        return words, self.word_pad_idx
 
     def _desc(self, B, K, R, eval_mode, C=0, Q=1, W=1, WL=0, train_pv=False):
         a = self.args
@@ -439,6 +472,7 @@ class ProductRanker(HotPathModule):
             want += [n for n in names if 'item' in n]
         for n in names:
             setattr(bt, n, None)
+        taken = {}
         for n in want:
             t = self._idx(getattr(batch, n, None), n)
             if t is None:
@@ -448,6 +482,8 @@ class ProductRanker(HotPathModule):
                 raise RuntimeError("batch.%s has shape %s, expected %s" % (n, tuple(t.shape), exp))
             setattr(bt, n, t.data_ptr())
             keep.append(t)
+            taken[n] = t
+        return taken
 
     @staticmethod
     def _idx(t, name, dtype=torch.int64):
@@ -570,10 +606,13 @@ class ProductRanker(HotPathModule):
                 raise RuntimeError("neg_word_idxs must hold B*R*W*K = %d draws" % (B * R * W * K))
             bt.neg_word_idxs = nw.data_ptr()
             keep.append(nw)
-        self._seq_ids(bt, b, ('pos_user_idxs', 'neg_user_idxs', 'pos_item_idxs', 'neg_item_idxs'),
-                      dict(pos_user_idxs=(B, R + 1), pos_item_idxs=(B, R + 1),
-                           neg_user_idxs=(B, K, R + 1), neg_item_idxs=(B, K, R + 1)), keep)
+        seq = self._seq_ids(bt, b, ('pos_user_idxs', 'neg_user_idxs', 'pos_item_idxs', 'neg_item_idxs'),
+                            dict(pos_user_idxs=(B, R + 1), pos_item_idxs=(B, R + 1),
+                                 neg_user_idxs=(B, K, R + 1), neg_item_idxs=(B, K, R + 1)), keep)
         plan.keep = keep
+        # what the kernels read, by name: the row-sparse optimizer's touched lists are built from these (_index_lists)
+        plan.lists = dict(seq, query_word_idxs=qw, pos_prod_ridxs=pr, neg_prod_ridxs=nr, pos_prod_rword_idxs=pw,
+                          neg_word_idxs=nw if train_pv else None)
         loss3 = torch.empty(3, device=self._dev(), dtype=torch.float32)
         _lib.check(lib.ps_rtm_forward(plan.desc, ps, bt, plan.ws.data_ptr(), loss3.data_ptr(), self._stream()),
                    'ps_rtm_forward')
@@ -583,9 +622,14 @@ class ProductRanker(HotPathModule):
         lib = _lib.load()
         ps, gs = self._structs()
         st = self._stream()
-        if self._assign_grads() and not self.__dict__.get('_grad_clean', False):     # (clean: the last optimizer step left the buffer at 0)
-            self._zero_for_backward()
+        if self._assign_grads():
+            if not self.__dict__.get('_grad_clean', False):     # (clean: the last optimizer step left the buffer at 0)
+                self._zero_for_backward()
+        else:
+            self._refuse_dirty_accumulation()
         self.__dict__['_grad_clean'] = False
+        if self._row_sparse():
+            self._coalesce_touched(plan)        # the lists need the step's indices only: three launches at the head
         go = None if grad_out is None else grad_out.contiguous().float()          # None: d loss / d loss = 1
         _lib.check(lib.ps_rtm_backward(plan.desc, ps, plan.batch, plan.ws.data_ptr(), gs, 1.0,
                                        None if go is None else go.data_ptr(), st), 'ps_rtm_backward')
