@@ -379,7 +379,9 @@ const int32_t* ps_coalesce_bad_flag(void* ws_dev, int64_t n_rows);
  * trainer.py:64-83).  Every rank packs a fixed-capacity message — msg_rows[cap]: its sorted touched ids, then -1;
  * msg_vals[cap,d]: their gradient rows, then zeros — the messages are all-gathered (RCCL), the union of the ids is
  * ps_coalesce_rows over the gathered ids with pad_row = -1, and ps_merge_rows writes, for every union row, the sum of the
- * ranks' rows IN RANK ORDER into the dense gradient: bitwise the same result on every rank.  world <= 32. */
+ * ranks' rows IN RANK ORDER into the dense gradient: bitwise the same result on every rank.  world <= 32, and
+ * d >= 4 * world: a row narrower than that leaves lanes that hold a rank's position outside ps_merge_rows' shuffle
+ * (ps_merge_tables below has no such limit). */
 int ps_pack_rows(const float* grad_dev, int32_t d, const int64_t* rows_dev, const int32_t* count_dev, int64_t cap,
                  int64_t* msg_rows_dev, float* msg_vals_dev, ps_stream_t stream);
 int ps_merge_rows(const int64_t* all_rows_dev, const float* all_vals_dev, int32_t world, int64_t cap, int32_t d,
@@ -671,6 +673,43 @@ typedef struct PsCoalesceTable {
   int32_t* count_out_dev;
 } PsCoalesceTable;
 int ps_coalesce_tables(const PsCoalesceTable* tabs_host, int32_t n_tabs, ps_stream_t stream);
+
+/* ------------------------------------------------------------------ several tables in one row exchange
+ * The data-parallel row exchange of ps_pack_rows / ps_coalesce_rows / ps_merge_rows for a model with several row-sparse
+ * tables: ONE message per rank, ONE all-gather, one pack launch, one union (three launches) and one merge launch per step.
+ * A rank's message is one byte buffer: for tables t = 0 .. n_tabs-1 first the id sections (cap_t int64: the rank's ascending
+ * touched ids, then -1), then the value sections (cap_t x d_t fp32: their gradient rows, then zeros).  Every section starts
+ * on a 16-byte boundary (the 8 bytes after an id section of odd capacity are written as -1) and the total is a multiple of 16, so slot r of the gathered [world, msg_bytes] buffer is aligned
+ * like the message; the bytes are a function of the gradient only.  ps_row_msg_layout is host-only arithmetic: the section
+ * offsets and the total from (cap_t, d_t); -1 (and ps_last_error) on a bad argument.  The three entries derive the same
+ * layout from their tables and refuse a msg_bytes that differs.  n_tabs 1..4, d % 4 == 0, world 1..32. */
+typedef struct PsRowMsgTable {
+  int64_t cap;                 /* message capacity in rows: the same on every rank */
+  int32_t d;
+  int32_t pad_;
+  int64_t n_rows;
+  float* grad_dev;             /* [n_rows, d] dense gradient: ps_pack_tables reads it, ps_merge_tables writes the union's rows */
+  const int64_t* rows_dev;     /* this rank's touched list (ps_coalesce_*): list_cap entries, *count_dev of them live */
+  const int32_t* count_dev;
+  int64_t list_cap;            /* <= cap */
+  void* ws_dev;                /* union: a ps_coalesce_ws_bytes(n_rows) workspace of its own (zeroed once, left zeroed) */
+  int64_t* union_rows_dev;     /* union_cap entries: the sorted unique ids over the ranks' sections */
+  int64_t union_cap;
+  int32_t* union_count_dev;
+} PsRowMsgTable;
+int64_t ps_row_msg_layout(const int64_t* caps_host, const int32_t* ds_host, int32_t n_tabs, int64_t* ids_off_out,
+                          int64_t* vals_off_out);
+/* msg_dev[msg_bytes] <- this rank's message.  Slots past *count_dev are written as -1 / zeros whatever the buffer held. */
+int ps_pack_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, void* msg_dev, int64_t msg_bytes, ps_stream_t stream);
+/* Per table the sorted unique ids over the `world` id sections of all_dev [world, msg_bytes] -> union_rows / union_count.
+ * Workspace, status word (ps_coalesce_bad_flag: 1 an id outside [0, n_rows), 2 more unique ids than union_cap — the call
+ * still returns PS_OK, the ids that fit are written, *union_count is the full count) and output are ps_coalesce_rows' own. */
+int ps_union_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, const void* all_dev, int64_t msg_bytes, int32_t world,
+                    ps_stream_t stream);
+/* grad[union row, :] = sum over ranks 0 .. world-1, in that order, of the rows the ranks sent for it (ps_merge_rows'
+ * arithmetic): bitwise the same on every rank.  Rows outside the union are not touched. */
+int ps_merge_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, const void* all_dev, int64_t msg_bytes, int32_t world,
+                    ps_stream_t stream);
 
 #ifdef __cplusplus
 }

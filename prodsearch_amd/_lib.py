@@ -78,6 +78,12 @@ class PsCoalesceTable(C.Structure):
                 ('cap', C.c_int64), ('count_out_dev', C.c_void_p)]
 
 
+class PsRowMsgTable(C.Structure):
+    _fields_ = [('cap', C.c_int64), ('d', C.c_int32), ('pad_', C.c_int32), ('n_rows', C.c_int64), ('grad_dev', C.c_void_p),
+                ('rows_dev', C.c_void_p), ('count_dev', C.c_void_p), ('list_cap', C.c_int64), ('ws_dev', C.c_void_p),
+                ('union_rows_dev', C.c_void_p), ('union_cap', C.c_int64), ('union_count_dev', C.c_void_p)]
+
+
 class PsRowTable(C.Structure):
     _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p),
                 ('rows', C.c_void_p), ('count', C.c_void_p), ('cap', C.c_int64), ('d', C.c_int32),
@@ -247,6 +253,11 @@ SYMBOLS = {
                                C.c_void_p]),
     'ps_merge_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    'ps_row_msg_layout': (C.c_int64, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64)]),
+    'ps_pack_tables': (C.c_int, [C.POINTER(PsRowMsgTable), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'ps_union_tables': (C.c_int, [C.POINTER(PsRowMsgTable), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    'ps_merge_tables': (C.c_int, [C.POINTER(PsRowMsgTable), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     'ps_adam_rowsparse_state_floats': (C.c_int64, [C.c_int32, C.POINTER(PsRowTable), C.c_int32]),
     'ps_clip_adam_rowsparse': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PsRowTable), C.c_int32,
                                          C.POINTER(PsAdamHyper), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -13,6 +13,7 @@ _DEFAULTS = dict(
     seed=666,
     row_sparse_adam=False,             # extension (no reference flag): touched-rows-only Adam/zero/exchange for huge tables
     shard_tables=False, lazy_exact_adam=False,                # extension (no reference flag): item table sharded by row over the ranks (sharded.py; implies row_sparse_adam)
+    max_query_len=None,                # extension: the corpus-wide padded query length; bounds the word table's row messages (ProductRanker._index_cap_bound)
     train_from='',
     model_name='item_transformer',     # main.py:29 (default there is review_transformer)
     sep_prod_emb=False,                # main.py:31

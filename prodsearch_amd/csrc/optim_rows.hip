@@ -422,8 +422,268 @@ extern "C" int ps_merge_rows(const int64_t* all_rows_dev, const float* all_vals_
   return PS_OK;
 }
 
+// ---------------------------------------------------------------- every table's rows in ONE message (ps_*_tables)
+// A model with T row-sparse tables would pay, table by table, 2 T all-gathers and 5 T launches for its exchange.  Here a
+// rank's message is ONE byte buffer — the id sections of all tables (cap_t int64 each: ascending touched ids, then -1), then
+// their value sections (cap_t x d_t fp32: the gradient rows, then zeros), every section on a 16-byte boundary, the total a
+// multiple of 16 — so one all-gather moves it, and pack / union / merge run once each over all tables: the pack and merge grids
+// are the concatenation of the tables' row blocks, the union's mark grid that of the gathered id slots; a block finds its table
+// in a prefix array that travels by value (co_find).  The union's count and emit stages are the coalesce kernels themselves.
+struct RowMsgLayout { int64_t ids_off[CO_MAX_TABLES], vals_off[CO_MAX_TABLES], bytes; };
+
+static int row_msg_layout(const char* who, const int64_t* caps, const int32_t* ds, int32_t n_tabs, RowMsgLayout* L) {
+  PS_REQUIRE(caps && ds, "%s: null argument", who);
+  PS_REQUIRE(n_tabs >= 1 && n_tabs <= CO_MAX_TABLES, "%s: 1..%d tables (%d given)", who, CO_MAX_TABLES, (int)n_tabs);
+  int64_t off = 0;
+  for (int t = 0; t < n_tabs; ++t) {
+    PS_REQUIRE(caps[t] > 0 && caps[t] < ((int64_t)1 << 31), "%s: table %d: capacity %lld", who, t, (long long)caps[t]);
+    PS_REQUIRE(ds[t] > 0 && ds[t] % 4 == 0, "%s: table %d: width %d is not a positive multiple of 4", who, t, (int)ds[t]);
+    L->ids_off[t] = off;
+    off += (caps[t] * 8 + 15) & ~(int64_t)15;
+  }
+  for (int t = 0; t < n_tabs; ++t) {
+    L->vals_off[t] = off;
+    off += caps[t] * (int64_t)ds[t] * 4;             // d % 4 == 0: a multiple of 16
+  }
+  L->bytes = off;
+  return PS_OK;
+}
+
+extern "C" int64_t ps_row_msg_layout(const int64_t* caps_host, const int32_t* ds_host, int32_t n_tabs, int64_t* ids_off_out,
+                                     int64_t* vals_off_out) {
+  RowMsgLayout L;
+  if (row_msg_layout("row_msg_layout", caps_host, ds_host, n_tabs, &L) != PS_OK) return -1;
+  for (int t = 0; t < n_tabs; ++t) {
+    if (ids_off_out) ids_off_out[t] = L.ids_off[t];
+    if (vals_off_out) vals_off_out[t] = L.vals_off[t];
+  }
+  return L.bytes;
+}
+
+// what the three entries check alike: the table count, the layout the tables' (cap, d) give against the caller's msg_bytes
+static int row_msg_check(const char* who, const PsRowMsgTable* tabs, int32_t n_tabs, const void* buf, int64_t msg_bytes,
+                         RowMsgLayout* L) {
+  PS_REQUIRE(tabs && n_tabs >= 1 && n_tabs <= CO_MAX_TABLES, "%s: 1..%d tables (%d given)", who, CO_MAX_TABLES, (int)n_tabs);
+  PS_REQUIRE(buf, "%s: null message buffer", who);
+  PS_REQUIRE((((uintptr_t)buf) & 15) == 0, "%s: message buffer not 16-byte aligned", who);
+  int64_t caps[CO_MAX_TABLES]; int32_t ds[CO_MAX_TABLES];
+  for (int t = 0; t < n_tabs; ++t) { caps[t] = tabs[t].cap; ds[t] = tabs[t].d; }
+  TRY(row_msg_layout(who, caps, ds, n_tabs, L));                  // (capacities 1 .. 2^31 - 1, widths a multiple of 4)
+  PS_REQUIRE(msg_bytes == L->bytes, "%s: msg_bytes %lld, the tables' layout has %lld", who, (long long)msg_bytes, (long long)L->bytes);
+  return PS_OK;
+}
+static int row_msg_world(const char* who, int32_t world) {
+  PS_REQUIRE(world >= 1 && world <= PS_MERGE_MAX_WORLD, "%s: world %d (1..%d)", who, (int)world, PS_MERGE_MAX_WORLD);
+  return PS_OK;
+}
+
+struct PackTab {
+  const float* grad; const int64_t* rows; const int32_t* count;
+  int64_t cap, list_cap, n_rows;
+  int64_t* ids; float* vals; int32_t d;
+};
+struct PackTabs { PackTab t[CO_MAX_TABLES]; int32_t blk0[CO_MAX_TABLES + 1]; int32_t n; };
+
+// rows_pack_kernel's message, every table in one launch: 32 lanes per slot, 16 B per lane, 8 slots per block.  The row id is
+// loaded from a clamped position of the list and the gradient row from a clamped row, both judged afterwards: no vector load
+// sits behind the bounds test.  A slot past the list's count (or holding an id outside the table, which a
+// coalesced list never does) is written as -1 / zeros, whatever the buffer held: the bytes are a function of the gradient only.
+__global__ __launch_bounds__(256) void rows_pack_tabs_kernel(PackTabs T) {
+  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const PackTab& tb = T.t[t];
+  const int64_t u = (int64_t)((int)blockIdx.x - T.blk0[t]) * 8 + (threadIdx.x >> 5);
+  const int lane = threadIdx.x & 31;
+  const int64_t n = (int64_t)*tb.count;
+  const int64_t r0 = tb.rows[u < tb.list_cap ? u : tb.list_cap - 1];
+  const bool live = u < n && u < tb.list_cap && r0 >= 0 && r0 < tb.n_rows;
+  const float4* g4 = (const float4*)(tb.grad + (live ? r0 : 0) * (int64_t)tb.d);
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4* v4 = (float4*)(tb.vals + u * (int64_t)tb.d);
+  const bool slot = u < tb.cap;                               // (the last block of a table whose cap is no multiple of 8)
+  for (int j = lane; j < tb.d / 4; j += 32) {
+    const float4 g = g4[j];
+    if (slot) v4[j] = live ? g : zero;
+  }
+  if (slot && lane == 0) tb.ids[u] = live ? r0 : -1;
+  if (lane == 1 && u == tb.cap - 1 && (tb.cap & 1)) tb.ids[tb.cap] = -1;     // the 8 bytes that round an odd section up to 16
+}
+
+extern "C" int ps_pack_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, void* msg_dev, int64_t msg_bytes,
+                              ps_stream_t stream) {
+  RowMsgLayout L;
+  TRY(row_msg_check("pack_tables", tabs_host, n_tabs, msg_dev, msg_bytes, &L));
+  PackTabs T = PackTabs();
+  T.n = n_tabs;
+  int64_t b = 0;
+  for (int t = 0; t < n_tabs; ++t) {
+    const PsRowMsgTable& h = tabs_host[t];
+    PS_REQUIRE(h.grad_dev && h.rows_dev && h.count_dev, "pack_tables: table %d: null pointer", t);
+    PS_REQUIRE((((uintptr_t)h.grad_dev) & 15) == 0, "pack_tables: table %d: gradient not 16-byte aligned", t);
+    PS_REQUIRE(h.n_rows > 0, "pack_tables: table %d: n_rows %lld", t, (long long)h.n_rows);
+    PS_REQUIRE(h.list_cap > 0 && h.list_cap <= h.cap, "pack_tables: table %d: list capacity %lld, message capacity %lld", t,
+               (long long)h.list_cap, (long long)h.cap);
+    PackTab& tb = T.t[t];
+    tb.grad = h.grad_dev; tb.rows = h.rows_dev; tb.count = h.count_dev;
+    tb.cap = h.cap; tb.list_cap = h.list_cap; tb.n_rows = h.n_rows; tb.d = h.d;
+    tb.ids = (int64_t*)((char*)msg_dev + L.ids_off[t]);
+    tb.vals = (float*)((char*)msg_dev + L.vals_off[t]);
+    T.blk0[t] = (int32_t)b;
+    b += (h.cap + 7) / 8;                                     // (cap < 2^31 each: at most 2^30 blocks)
+  }
+  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) T.blk0[t] = (int32_t)b;
+  hipStream_t st = (hipStream_t)stream;
+  KTimeScope kt("pack_tables", st);
+  PS_KLAUNCH(rows_pack_tabs_kernel, dim3((unsigned)b), dim3(256), 0, st, T);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// the union's mark stage over strided segments: slot i of table t is id u = i % cap of rank r = i / cap, at
+// base + r * stride (bytes) + 8 u; -1 is the pad.  co_mark_tabs_kernel's discipline: the id is loaded from a clamped slot, the
+// bitmap word from a clamped row, and both are judged afterwards.  The bitmaps, block sums, status words and outputs sit in
+// the CoTabs the count and emit kernels take (its index lists stay empty: the segments are not index lists).
+struct CoSegs { const char* base[CO_MAX_TABLES]; int64_t cap[CO_MAX_TABLES]; int64_t total[CO_MAX_TABLES]; int64_t stride; };
+
+__global__ __launch_bounds__(256) void co_mark_segs_kernel(CoTabs T, CoSegs S) {
+  const int t = co_find(T.mblk0, T.n, (int)blockIdx.x);
+  const CoTab& tb = T.t[t];
+  const int64_t i0 = (int64_t)((int)blockIdx.x - T.mblk0[t]) * 256 + threadIdx.x;
+  const int64_t i = i0 < S.total[t] ? i0 : S.total[t] - 1;
+  const uint32_t rk = (uint32_t)i / (uint32_t)S.cap[t], u = (uint32_t)i - rk * (uint32_t)S.cap[t];    // (total < 2^31: host check)
+  const int64_t r = ((const int64_t*)(S.base[t] + rk * S.stride))[u];
+  const bool live = i0 < S.total[t] && r != -1;
+  const bool in = r >= 0 && r < tb.n_rows;
+  const int64_t rr = in ? r : 0;
+  const unsigned long long bit = 1ull << (rr & 63);
+  const unsigned long long seen = __builtin_nontemporal_load(&tb.bitmap[rr >> 6]);
+  if (!live) return;
+  if (!in) { *tb.bad = 1; return; }
+  if (!(seen & bit)) atomicOr(&tb.bitmap[rr >> 6], bit);      // an id every rank sent repeats world times
+}
+
+extern "C" int ps_union_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, const void* all_dev, int64_t msg_bytes,
+                               int32_t world, ps_stream_t stream) {
+  RowMsgLayout L;
+  TRY(row_msg_check("union_tables", tabs_host, n_tabs, all_dev, msg_bytes, &L));
+  TRY(row_msg_world("union_tables", world));
+  CoTabs T = CoTabs();
+  CoSegs S = CoSegs();
+  T.n = n_tabs;
+  S.stride = msg_bytes;
+  int64_t mb = 0, cb = 0;
+  for (int t = 0; t < n_tabs; ++t) {
+    const PsRowMsgTable& h = tabs_host[t];
+    CoTab& tb = T.t[t];
+    PS_REQUIRE(h.ws_dev && h.union_rows_dev && h.union_count_dev, "union_tables: table %d: null pointer", t);
+    PS_REQUIRE(h.n_rows > 0 && h.n_rows < ((int64_t)1 << 37), "union_tables: table %d: n_rows %lld", t, (long long)h.n_rows);
+    PS_REQUIRE(h.union_cap > 0, "union_tables: table %d: union capacity %lld", t, (long long)h.union_cap);
+    for (int u = 0; u < t; ++u)
+      PS_REQUIRE(tabs_host[u].ws_dev != h.ws_dev, "union_tables: tables %d and %d share a workspace", u, t);
+    tb.L.n = 0; tb.L.total = 0;
+    tb.n_rows = h.n_rows; tb.pad_row = -1; tb.n_words = co_words(h.n_rows);
+    tb.bitmap = (unsigned long long*)h.ws_dev;
+    tb.blocksum = (int32_t*)(tb.bitmap + tb.n_words);
+    tb.bad = tb.blocksum + co_blocks(h.n_rows);
+    tb.rows = h.union_rows_dev; tb.cap = h.union_cap; tb.count = h.union_count_dev;
+    S.base[t] = (const char*)all_dev + L.ids_off[t];
+    S.cap[t] = h.cap; S.total[t] = (int64_t)world * h.cap;
+    PS_REQUIRE(S.total[t] < ((int64_t)1 << 31), "union_tables: table %d: too many id slots", t);
+    T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb;
+    mb += (S.total[t] + 255) / 256;                           // (< 2^23 blocks a table, and so is the next line's)
+    cb += co_blocks(h.n_rows);
+  }
+  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) { T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb; }
+  hipStream_t st = (hipStream_t)stream;
+  { KTimeScope kt("union_mark", st); PS_KLAUNCH(co_mark_segs_kernel, dim3((unsigned)mb), dim3(256), 0, st, T, S); }
+  PS_LAUNCH_CHECK();
+  { KTimeScope kt("union_count", st); PS_KLAUNCH(co_count_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T); }
+  PS_LAUNCH_CHECK();
+  { KTimeScope kt("union_emit", st); PS_KLAUNCH(co_emit_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T); }
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// rows_merge_kernel over all tables: per union row, lane r < world binary-searches rank r's id section, then all 32 lanes add
+// the found rows in rank order 0 .. world-1 — the same addends in the same order as ps_merge_rows, on every rank.
+struct MergeTab {
+  const char* ids; const char* vals;            // rank 0's sections; rank r's are `stride` bytes further each
+  int64_t cap, union_cap; int32_t d;
+  float* grad; const int64_t* u_rows; const int32_t* u_count;
+};
+struct MergeTabs { MergeTab t[CO_MAX_TABLES]; int32_t blk0[CO_MAX_TABLES + 1]; int32_t n; int32_t world; int64_t stride; };
+
+__global__ __launch_bounds__(256) void rows_merge_tabs_kernel(MergeTabs T) {
+  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const MergeTab& tb = T.t[t];
+  const int64_t u = (int64_t)((int)blockIdx.x - T.blk0[t]) * 8 + (threadIdx.x >> 5);
+  const int lane = threadIdx.x & 31;
+  const int64_t cap = tb.cap;
+  const int d = tb.d;
+  // (a union that overflowed its capacity reports the full count: only the rows that were written exist)
+  const bool live = u < (int64_t)*tb.u_count && u < tb.union_cap;          // uniform per 32-lane group
+  int64_t found = -1;
+  const int64_t row = live ? tb.u_rows[u] : -1;
+  if (live && lane < T.world) {
+    const int64_t* lst = (const int64_t*)(tb.ids + (size_t)lane * T.stride);   // ascending ids, then -1 padding (= +infinity here)
+    int64_t lo = 0, hi = cap;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      const int64_t v = lst[mid];
+      if (v >= 0 && v < row) lo = mid + 1; else hi = mid;
+    }
+    if (lo < cap && lst[lo] == row) found = lo;
+  }
+  if (!live) return;
+  float4* g4 = (float4*)(tb.grad + row * (int64_t)d);
+  // the trip count is the group's, not the lane's: lane r must be in the shuffle that reads its position even when the row
+  // has fewer float4s than the world has ranks (d = 4: one lane holds data)
+  for (int j0 = 0; j0 < d / 4; j0 += 32) {
+    const int j = j0 + lane;
+    const bool mine = j < d / 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = 0; r < T.world; ++r) {
+      const int64_t pos = __shfl(found, (threadIdx.x & 32) + r, 64);
+      if (pos >= 0 && mine) {
+        const float4 x = ((const float4*)(tb.vals + (size_t)r * T.stride + (size_t)pos * d * 4))[j];
+        acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+      }
+    }
+    if (mine) g4[j] = acc;
+  }
+}
+
+extern "C" int ps_merge_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, const void* all_dev, int64_t msg_bytes,
+                               int32_t world, ps_stream_t stream) {
+  RowMsgLayout L;
+  TRY(row_msg_check("merge_tables", tabs_host, n_tabs, all_dev, msg_bytes, &L));
+  TRY(row_msg_world("merge_tables", world));
+  MergeTabs T = MergeTabs();
+  T.n = n_tabs; T.world = world; T.stride = msg_bytes;
+  int64_t b = 0;
+  for (int t = 0; t < n_tabs; ++t) {
+    const PsRowMsgTable& h = tabs_host[t];
+    PS_REQUIRE(h.grad_dev && h.union_rows_dev && h.union_count_dev, "merge_tables: table %d: null pointer", t);
+    PS_REQUIRE((((uintptr_t)h.grad_dev) & 15) == 0, "merge_tables: table %d: gradient not 16-byte aligned", t);
+    PS_REQUIRE(h.union_cap > 0, "merge_tables: table %d: union capacity %lld", t, (long long)h.union_cap);
+    MergeTab& tb = T.t[t];
+    tb.ids = (const char*)all_dev + L.ids_off[t]; tb.vals = (const char*)all_dev + L.vals_off[t];
+    tb.cap = h.cap; tb.union_cap = h.union_cap; tb.d = h.d;
+    tb.grad = h.grad_dev; tb.u_rows = h.union_rows_dev; tb.u_count = h.union_count_dev;
+    T.blk0[t] = (int32_t)b;
+    b += (h.union_cap + 7) / 8;
+    PS_REQUIRE(b < ((int64_t)1 << 31), "merge_tables: grid too large");
+  }
+  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) T.blk0[t] = (int32_t)b;
+  hipStream_t st = (hipStream_t)stream;
+  KTimeScope kt("merge_tables", st);
+  PS_KLAUNCH(rows_merge_tabs_kernel, dim3((unsigned)b), dim3(256), 0, st, T);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
 // ---------------------------------------------------------------- row-sparse clip + Adam
 #define RS_MAX_TABLES 4
+
 #define RS_ROWS_PER_BLOCK 8
 struct RowTables { PsRowTable t[RS_MAX_TABLES]; int32_t blk0[RS_MAX_TABLES + 1]; int32_t n; };
 

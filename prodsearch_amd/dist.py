@@ -218,16 +218,146 @@ class SparseGradExchange(object):
         return None
 
 
-def _refuse_frozen_words(model):
-    """Data parallelism with a frozen word table (pretrain_emb_dir / requires_grad False) is not built: refused up front."""
+def row_msg_layout(caps, ds):
+    """(id section offsets, value section offsets, bytes) of one rank's message for tables of capacities ``caps`` (rows) and
+    widths ``ds``: ``ps_row_msg_layout``, host-only arithmetic (no GPU is touched)."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.load()
+    n = len(caps)
+    ca, da = (C.c_int64 * max(n, 1))(*caps), (C.c_int32 * max(n, 1))(*ds)
+    io, vo = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    nbytes = lib.ps_row_msg_layout(ca, da, n, io, vo)
+    if nbytes < 0:
+        _lib.check(1, 'ps_row_msg_layout')
+    return list(io[:n]), list(vo[:n]), int(nbytes)
+
+
+class TablesGradExchange(object):
+    """``SparseGradExchange``'s protocol with every row-sparse table of the model in ONE message (``mode='tables'``).
+
+    Table by table the row exchange costs two all-gathers and five launches per table — 8 latency-bound collectives and 20
+    launches for the review transformer's four tables, on a step whose whole backward is a few launches.  Here a rank's
+    message is one byte buffer (``ps_row_msg_layout``: the tables' id sections, then their value sections, 16-byte aligned),
+    and a step is: the all-reduce of the small tensors, ``ps_pack_tables`` (one launch), ONE all-gather, ``ps_union_tables``
+    (three launches: a strided mark + the coalesce kernels' count and emit) and ``ps_merge_tables`` (one launch, rank-ordered
+    sums: replicas bitwise identical).  The union becomes the touched list the optimizer and ``zero_grad`` walk.  No host
+    synchronisation: the capacities are agreed ONCE, at the first exchange, by one MAX all-reduce over a vector with one
+    entry per table — max(this step's capacity, ``model._index_cap_bound(path)``), clamped to the table's rows — and a later
+    step whose local capacity exceeds the agreement raises before any collective is entered.  Works over
+    ``model._sparse_tabs`` of any row-sparse model (the item models' default stays ``SparseGradExchange``)."""
+
+    def __init__(self, model, optim=None, group=None):
+        _refuse_frozen_words(model, tables=True)
+        a = getattr(model, 'args', None)
+        if getattr(a, 'lazy_exact_adam', False):
+            raise NotImplementedError("mode='tables': lazy_exact_adam is not supported by the one-message row exchange")
+        if getattr(a, 'shard_tables', False) or model.__dict__.get('_shard') is not None:
+            raise NotImplementedError("mode='tables': shard_tables is not supported by the one-message row exchange")
+        if not getattr(model, '_row_sparse', lambda: False)():
+            raise NotImplementedError("mode='tables' exchanges touched rows: this model is not row-sparse "
+                                      "(args.row_sparse_adam is off)")
+        self.model = model
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self._flat = _flat_gather_supported(group) if self.world > 1 else True
+        self._caps = None            # per table of model._sparse_tabs: the message capacity every rank agreed on (rows)
+        self._msg = None
+        if optim is not None:
+            optim.grad_scale = 1.0 / self.world
+
+    def _agree_capacities(self, bounds, tabs):
+        """ONE MAX all-reduce over the vector of the tables' bounds (one host sync, first exchange only: every rank is in
+        that step).  Later steps never re-negotiate — a collective only some ranks enter would hang."""
+        t = torch.tensor([int(b) for b in bounds], dtype=torch.int64, device=tabs[0][1].device)
+        with _comm('all_reduce(row capacities)'):
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        self._caps = [max(1, min(int(c), p.shape[0])) for c, (_, p, _) in zip(t.tolist(), tabs)]
+
+    def _buffers(self, tabs):
+        W = self.world
+        key = (tuple(self._caps), tuple(p.shape[1] for _, p, _ in tabs), W)
+        if self._msg is None or self._msg['key'] != key:
+            dev = tabs[0][1].device
+            _, _, nbytes = row_msg_layout(self._caps, [p.shape[1] for _, p, _ in tabs])
+            self._msg = dict(key=key, bytes=nbytes, mine=torch.empty(nbytes, device=dev, dtype=torch.uint8),
+                             all=torch.empty(W, nbytes, device=dev, dtype=torch.uint8))
+        return self._msg
+
+    def _table_buffers(self, info, p, cap):
+        x = info.get('xchg')
+        if x is None or x['cap'] != cap or x['world'] != self.world:
+            from . import _lib
+            dev = p.device
+            ucap = max(1, min(self.world * cap, p.shape[0]))
+            x = dict(cap=cap, world=self.world, ucap=ucap,
+                     urows=torch.empty(ucap, device=dev, dtype=torch.int64),
+                     ucount=torch.zeros(1, device=dev, dtype=torch.int32),
+                     ws=torch.zeros(_lib.load().ps_coalesce_ws_bytes(p.shape[0]), device=dev, dtype=torch.uint8))
+            info['xchg'] = x         # (HotPathModule.check_index_errors reads the union's status word from x['ws'])
+        return x
+
+    def message_bytes(self):
+        """Bytes of one rank's message (None before the first exchange)."""
+        return None if self._msg is None else self._msg['bytes']
+
+    def __call__(self):
+        if self.world == 1:
+            return None
+        from . import _lib
+        lib = _lib.load()
+        m = self.model
+        tabs = m._sparse_tabs
+        if not tabs:
+            raise RuntimeError("mode='tables': the model has no row-sparse table to exchange")
+        # capacities first (first step only), and the local check, BEFORE any collective of this step is entered
+        local = [int(p._ps_rows['cap']) for _, p, _ in tabs]
+        if self._caps is None:
+            self._agree_capacities([max(c, m._index_cap_bound(path)) for c, (path, _, _) in zip(local, tabs)], tabs)
+        for c, cap, (path, _, _) in zip(local, self._caps, tabs):
+            if c > cap:
+                raise RuntimeError("row exchange: this rank's step addresses up to %d rows of %s but the ranks agreed on "
+                                   "messages of %d rows at the first step; set args.batch_size / uprev_review_limit / "
+                                   "iprev_review_limit / max_query_len to the largest batch any rank will see"
+                                   % (c, '.'.join(path), cap))
+        msg = self._buffers(tabs)
+        arr = (_lib.PsRowMsgTable * len(tabs))()
+        for t, (_, p, gview), c, cap in zip(arr, tabs, local, self._caps):
+            info = p._ps_rows
+            x = self._table_buffers(info, p, cap)
+            t.cap, t.d, t.n_rows, t.grad_dev = cap, p.shape[1], p.shape[0], gview.data_ptr()
+            t.rows_dev, t.count_dev, t.list_cap = info['rows'].data_ptr(), info['count'].data_ptr(), c
+            t.ws_dev, t.union_rows_dev, t.union_cap = x['ws'].data_ptr(), x['urows'].data_ptr(), x['ucap']
+            t.union_count_dev = x['ucount'].data_ptr()
+        st = torch.cuda.current_stream(tabs[0][1].device).cuda_stream
+        n, nbytes = len(tabs), msg['bytes']
+        with _comm('all_reduce(small tensors)'):
+            dist.all_reduce(m._grad_flat[:getattr(m, '_n_allreduce_grad', m._n_dense_grad)], op=dist.ReduceOp.SUM, group=self.group)
+        _lib.check(lib.ps_pack_tables(arr, n, msg['mine'].data_ptr(), nbytes, st), 'ps_pack_tables')
+        with _comm('all_gather(row message)'):
+            _all_gather_flat(msg['all'], msg['mine'], self.world, self.group, self._flat)
+        _lib.check(lib.ps_union_tables(arr, n, msg['all'].data_ptr(), nbytes, self.world, st), 'ps_union_tables')
+        _lib.check(lib.ps_merge_tables(arr, n, msg['all'].data_ptr(), nbytes, self.world, st), 'ps_merge_tables')
+        for _, p, _ in tabs:
+            x = p._ps_rows['xchg']
+            p._ps_rows['active'] = (x['urows'], x['ucount'], x['ucap'])     # what the optimizer / zero_grad walk this step
+        return None
+
+
+def _refuse_frozen_words(model, tables=False):
+    """Data parallelism with a frozen word table (pretrain_emb_dir / requires_grad False) is not built: refused up front.
+    ``tables``: the caller is the one-message row exchange, which serves the row-sparse review transformer."""
     w = getattr(model, 'word_embeddings', None)
     if w is not None and not w.weight.requires_grad:
         raise NotImplementedError("data-parallel training with a frozen word table (pretrain_emb_dir) is not supported")
     # the review transformer's other tables (pretrain_emb_dir's doc_emb, fix_emb, pretrain_up_emb_dir): same refusal
     tabs = getattr(model, '_hot_tables', None)
-    if tabs is not None and getattr(model, '_row_sparse', lambda: False)():
-        # the review transformer's touched lists have no row exchange yet (SparseGradExchange serves the item models)
-        raise NotImplementedError("data-parallel training of the review transformer with row_sparse_adam is not supported")
+    if tabs is not None and not tables and getattr(model, '_row_sparse', lambda: False)():
+        # the review transformer's touched lists travel in TablesGradExchange's one message only: the table-by-table
+        # SparseGradExchange (8 all-gathers a step for its four tables) and the flat parameter buffer are not built for it
+        raise NotImplementedError("data-parallel training of the review transformer with row_sparse_adam is not supported "
+                                  "by this exchange: use make_exchange(model, optim, group, mode='tables') or "
+                                  "PS_DP_EXCHANGE=tables (dist.TablesGradExchange)")
     for name, p in (tabs() if tabs is not None else {}).items():
         if not p.requires_grad:
             raise NotImplementedError("data-parallel training with a frozen %s table (pretrain_emb_dir / "
@@ -524,7 +654,11 @@ class ShardedAdamExchange(object):
 def make_exchange(model, optim=None, group=None, mode=None):
     """The exchange matching the model's optimizer mode.  Dense mode: ``sharded`` (reduce-scatter -> owner clip+Adam ->
     all-gather, the default when there is more than one rank and an optimizer to shard) or ``allreduce`` (one flat
-    all-reduce, every rank runs the whole optimizer; PS_DP_EXCHANGE=allreduce or ``mode=``)."""
+    all-reduce, every rank runs the whole optimizer; PS_DP_EXCHANGE=allreduce or ``mode=``).  Row-sparse mode: the item
+    models get ``SparseGradExchange``; ``mode='tables'`` (or PS_DP_EXCHANGE=tables) gives any row-sparse model — the review
+    transformer among them, which has no other row exchange — ``TablesGradExchange``: every table in one message."""
+    if (mode or os.environ.get('PS_DP_EXCHANGE')) == 'tables':
+        return TablesGradExchange(model, optim, group)
     _refuse_frozen_words(model)
     if getattr(model, '_row_sparse', lambda: False)():
         return SparseGradExchange(model, optim, group)

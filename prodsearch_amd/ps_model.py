@@ -444,6 +444,26 @@ class ProductRanker(HotPathModule):
             words += [ls['pos_prod_rword_idxs'], ls['neg_word_idxs']]
         return words, self.word_pad_idx
 
+    def _index_cap_bound(self, path):
+        """Largest index count a batch of ``args.batch_size`` entries can address in ``path``'s table, whatever the batch:
+        the sequence width is padded per batch (<= R = uprev_review_limit + iprev_review_limit), every entry brings
+        ``neg_per_pos`` negative sequences, and the user / item ids have one more position than the reviews.  The word
+        table (row-sparse under pv only) sees the queries and, in a PV step, ``pv_window_size`` words per positive review
+        with ``neg_per_pos`` draws each.  ``args.max_query_len`` is the corpus-wide padded query length; left at None the
+        word table's bound is its row count — safe, the message is merely larger.  The data-parallel row exchange sizes its
+        fixed-capacity messages with the maximum of this over the ranks (dist.TablesGradExchange)."""
+        a = self.args
+        B, K = int(a.batch_size), int(a.neg_per_pos)
+        R = int(a.uprev_review_limit) + int(a.iprev_review_limit)
+        if path == ('review_emb',):
+            return B * (1 + K) * R
+        if path in (('user_emb',), ('product_emb',)):
+            return B * (1 + K) * (R + 1)
+        Qmax = getattr(a, 'max_query_len', None)
+        if Qmax is None:
+            return int(self.word_embeddings.weight.shape[0])
+        return B * int(Qmax) + B * R * max(1, int(a.pv_window_size)) * (1 + K)
+
     def _desc(self, B, K, R, eval_mode, C=0, Q=1, W=1, WL=0, train_pv=False):
         a = self.args
         d = _lib.PsRtmDesc()
