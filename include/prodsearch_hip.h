@@ -360,7 +360,8 @@ int ps_rank_shard(const float* q, int32_t B, int32_t d, const float* table, int6
 typedef struct PsIdxList { const int64_t* idx; int64_t n; } PsIdxList;   /* device pointer, element count */
 
 /* Sorted unique row ids (!= pad_row) over up to 8 index lists -> rows_out[0..*count).  ws = ps_coalesce_ws_bytes
- * bytes, zeroed once by the caller and left zeroed by every call.  cap >= min(sum n, n_rows). */
+ * bytes, zeroed once by the caller and left zeroed by every call.  cap >= min(sum n, n_rows).  The one-table form of
+ * ps_coalesce_tables (below): the same kernels, launched over one table. */
 int64_t ps_coalesce_ws_bytes(int64_t n_rows);
 int ps_coalesce_rows(const PsIdxList* lists_host, int32_t n_lists, int64_t n_rows, int64_t pad_row, void* ws_dev,
                      int64_t* rows_out_dev, int64_t cap, int32_t* count_out_dev, ps_stream_t stream);
@@ -379,11 +380,14 @@ const int32_t* ps_coalesce_bad_flag(void* ws_dev, int64_t n_rows);
  * trainer.py:64-83).  Every rank packs a fixed-capacity message — msg_rows[cap]: its sorted touched ids, then -1;
  * msg_vals[cap,d]: their gradient rows, then zeros — the messages are all-gathered (RCCL), the union of the ids is
  * ps_coalesce_rows over the gathered ids with pad_row = -1, and ps_merge_rows writes, for every union row, the sum of the
- * ranks' rows IN RANK ORDER into the dense gradient: bitwise the same result on every rank.  world <= 32, and
- * d >= 4 * world: a row narrower than that leaves lanes that hold a rank's position outside ps_merge_rows' shuffle
- * (ps_merge_tables below has no such limit). */
-int ps_pack_rows(const float* grad_dev, int32_t d, const int64_t* rows_dev, const int32_t* count_dev, int64_t cap,
-                 int64_t* msg_rows_dev, float* msg_vals_dev, ps_stream_t stream);
+ * ranks' rows IN RANK ORDER into the dense gradient: bitwise the same result on every rank.  world <= 32, d % 4 == 0.
+ * These are the one-table forms of ps_pack_tables / ps_merge_tables (below), with the id and value sections in buffers
+ * of their own: all_rows [world, cap], all_vals [world, cap, d].
+ * ps_pack_rows: grad_dev [n_rows, d]; rows_dev holds list_cap entries (the touched list's allocation, 1 <= list_cap <= cap),
+ * *count_dev of them live.  msg_rows[u] / msg_vals[u, :] for u < cap: the list's id and its gradient row, or -1 / zeros for
+ * a slot past the count, past list_cap or holding an id outside [0, n_rows) — nothing past list_cap is read. */
+int ps_pack_rows(const float* grad_dev, int32_t d, int64_t n_rows, const int64_t* rows_dev, const int32_t* count_dev,
+                 int64_t list_cap, int64_t cap, int64_t* msg_rows_dev, float* msg_vals_dev, ps_stream_t stream);
 int ps_merge_rows(const int64_t* all_rows_dev, const float* all_vals_dev, int32_t world, int64_t cap, int32_t d,
                   float* grad_dev, const int64_t* union_rows_dev, const int32_t* union_count_dev, int64_t union_cap,
                   ps_stream_t stream);
@@ -658,7 +662,8 @@ int ps_gemm_f32(const float* A, int lda, int ta, const float* Bm, int ldb, int t
 
 /* ------------------------------------------------------------------ several tables in one coalesce
  * A model with several row-sparse tables (the review transformer: review / user / item / word) builds all its touched lists
- * in THREE launches instead of three per table.  Each entry is what one ps_coalesce_rows call takes — 1..8 index lists,
+ * in THREE launches instead of three per table (ps_coalesce_rows is this entry with one table).  Each entry is what one
+ * ps_coalesce_rows call takes — 1..8 index lists,
  * n_rows, pad_row, the table's own workspace (ps_coalesce_ws_bytes, zeroed once, left zeroed), rows_out / cap / count_out —
  * and gets what that call gives: the sorted unique non-pad ids, bit for bit, and the same status word (ps_coalesce_bad_flag:
  * 1 an id outside [0, n_rows) was dropped, 2 more unique rows than cap), set for that table only.  n_tabs 1..4. */

@@ -2,105 +2,32 @@
 // (SURVEY.md §8b ps_coalesce_rows / ps_adam_rowsparse, §8d config 5: 50 M × 256 table).
 //
 // The embedding gradients stay DENSE tensors, as nn.Embedding(sparse=False) gives the reference
-// (models/item_transformer.py:46,70); what becomes sparse is who touches them:
-//   ps_coalesce_rows      sorted unique non-pad row ids of a step's index lists.  Bitmap of one bit per
+// (models/item_transformer.py:46,70); what becomes sparse is who touches them.  Everything that works on row ids — the
+// coalesce, the pack / union / merge of the data-parallel exchange, the clip + Adam — is ONE kernel set over up to four
+// tables: the grid is the concatenation of the tables' blocks, the tables travel by value with a prefix array of their first
+// blocks, and a block finds its table there (tab_find).  The one-table entries (ps_coalesce_rows, ps_pack_rows,
+// ps_merge_rows) fill one table and go through the launch helper of their ps_*_tables entry.
+//   ps_coalesce_rows / _tables  sorted unique non-pad row ids of a step's index lists.  Bitmap of one bit per
 //                         table row (atomicOr), popcount per 256-word segment, ordered emit that also
 //                         clears the bitmap.  Deterministic, no sort, 3 launches, 6 MB of bitmap at 50 M rows.
 //   ps_gather_rows        values[u,:] = grad[rows[u],:]  (payload of the sparse gradient exchange)
 //   ps_scatter_rows       grad[rows[u],:] = values[u,:]  (merged gradient back into the dense tensor)
+//   ps_pack_rows / _tables, ps_union_tables, ps_merge_rows / _tables   the data-parallel exchange of touched rows
 //   ps_clip_adam_rowsparse  global-norm clip over (dense small tensors + touched rows) and Adam on exactly
 //                         those; touched gradient rows are re-zeroed in the same pass, so zero_grad never
 //                         streams the table.  Untouched rows keep p, m, v (the lazy "SparseAdam" rule;
 //                         dense Adam would keep decaying their moments — DESIGN.md §5b).
 #include "optim_core.h"
 
-#define CO_WORDS_PER_THREAD 1
-#define CO_WORDS_PER_BLOCK (256 * CO_WORDS_PER_THREAD)
+#define CO_WORDS_PER_BLOCK 256        // one bitmap word per thread
 #define PS_MAX_IDX_LISTS 8
+#define ROWS_MAX_TABLES 4
 
-struct IdxLists { PsIdxList l[PS_MAX_IDX_LISTS]; int32_t n; int64_t total; };
-
-__global__ __launch_bounds__(256) void co_mark_kernel(IdxLists L, int64_t n_rows, int64_t pad_row,
-                                                      unsigned long long* bitmap, int32_t* bad) {
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= L.total) return;
+// the table of block `blk`: blk0[k] = first block of table k (n tables, at most ROWS_MAX_TABLES; the array travels by value)
+__device__ inline int tab_find(const int32_t* blk0, int n, int blk) {
   int k = 0;
-  while (k < L.n - 1 && i >= L.l[k].n) { i -= L.l[k].n; ++k; }
-  const int64_t r = L.l[k].idx[i];
-  if (r == pad_row) return;
-  if (r < 0 || r >= n_rows) { *bad = 1; return; }
-  const unsigned long long bit = 1ull << (r & 63);
-  // popular rows (Zipf words) repeat thousands of times: skip the atomic once the bit is visible
-  if (__builtin_nontemporal_load(&bitmap[r >> 6]) & bit) return;
-  atomicOr(&bitmap[r >> 6], bit);
-}
-
-__global__ __launch_bounds__(256) void co_count_kernel(const unsigned long long* bitmap, int64_t n_words,
-                                                       int32_t* blocksum) {
-  __shared__ float shf[4];
-  (void)shf;
-  __shared__ int sh[4];
-  const int64_t w0 = (int64_t)blockIdx.x * CO_WORDS_PER_BLOCK + (int64_t)threadIdx.x * CO_WORDS_PER_THREAD;
-  int c = 0;
-#pragma unroll
-  for (int j = 0; j < CO_WORDS_PER_THREAD; ++j)
-    if (w0 + j < n_words) c += __popcll(bitmap[w0 + j]);
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) blocksum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-__global__ __launch_bounds__(256) void co_emit_kernel(unsigned long long* bitmap, int64_t n_words,
-                                                      const int32_t* blocksum, int64_t* rows, int64_t cap,
-                                                      int32_t* count_out, int32_t* bad) {
-  __shared__ int sh[256];
-  __shared__ int base_sh;
-  // rows emitted by earlier blocks
-  int part = 0;
-  part = strided_sum_i32<4>(blocksum, (int)blockIdx.x, threadIdx.x, 256);
-  sh[threadIdx.x] = part;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) base_sh = sh[0];
-  __syncthreads();
-  const int base = base_sh;
-  __syncthreads();
-  const int64_t w0 = (int64_t)blockIdx.x * CO_WORDS_PER_BLOCK + (int64_t)threadIdx.x * CO_WORDS_PER_THREAD;
-  unsigned long long w[CO_WORDS_PER_THREAD];
-  int c = 0;
-#pragma unroll
-  for (int j = 0; j < CO_WORDS_PER_THREAD; ++j) {
-    w[j] = (w0 + j < n_words) ? bitmap[w0 + j] : 0ull;
-    c += __popcll(w[j]);
-  }
-  // exclusive scan of c over the block (Hillis-Steele in LDS)
-  sh[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    int add = ((int)threadIdx.x >= o) ? sh[threadIdx.x - o] : 0;
-    __syncthreads();
-    sh[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int64_t pos = (int64_t)base + sh[threadIdx.x] - c;
-  if (c) {
-#pragma unroll
-    for (int j = 0; j < CO_WORDS_PER_THREAD; ++j) {
-      unsigned long long x = w[j];
-      while (x) {
-        const int b = __ffsll((long long)x) - 1;
-        x &= x - 1;
-        if (pos < cap) rows[pos] = (w0 + j) * 64 + b; else *bad = 2;
-        ++pos;
-      }
-      if (w[j]) bitmap[w0 + j] = 0ull;          // leave the bitmap clean for the next step
-    }
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) *count_out = base + sh[255];
+  while (k < n - 1 && blk >= blk0[k + 1]) ++k;
+  return k;
 }
 
 static inline int64_t co_words(int64_t n_rows) { return (n_rows + 63) / 64; }
@@ -112,62 +39,21 @@ extern "C" int64_t ps_coalesce_ws_bytes(int64_t n_rows) {
   return 8 * co_words(n_rows) + 4 * co_blocks(n_rows) + 16;
 }
 
-extern "C" int ps_coalesce_rows(const PsIdxList* lists_host, int32_t n_lists, int64_t n_rows, int64_t pad_row,
-                                void* ws_dev, int64_t* rows_out_dev, int64_t cap, int32_t* count_out_dev,
-                                ps_stream_t stream) {
-  PS_REQUIRE(lists_host && n_lists > 0 && n_lists <= PS_MAX_IDX_LISTS, "coalesce: 1..%d index lists", PS_MAX_IDX_LISTS);
-  PS_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 37) && ws_dev && rows_out_dev && count_out_dev && cap > 0,
-             "coalesce: bad argument");
-  IdxLists L;
-  L.n = n_lists; L.total = 0;
-  for (int i = 0; i < n_lists; ++i) {
-    PS_REQUIRE(lists_host[i].n >= 0 && (lists_host[i].n == 0 || lists_host[i].idx), "coalesce: list %d null", i);
-    L.l[i] = lists_host[i];
-    L.total += lists_host[i].n;
-  }
-  const int64_t need = L.total < n_rows ? L.total : n_rows;
-  PS_REQUIRE(cap >= need, "coalesce: rows_out capacity %lld < %lld", (long long)cap, (long long)need);
-  PS_REQUIRE(L.total < ((int64_t)1 << 31), "coalesce: too many indices");
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long* bitmap = (unsigned long long*)ws_dev;
-  const int64_t nw = co_words(n_rows), nb = co_blocks(n_rows);
-  int32_t* blocksum = (int32_t*)(bitmap + nw);
-  int32_t* bad = blocksum + nb;
-  if (L.total > 0) {
-    hipLaunchKernelGGL(co_mark_kernel, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, st, L, n_rows, pad_row,
-                       bitmap, bad);
-    PS_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(co_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, bitmap, nw, blocksum);
-  PS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(co_emit_kernel, dim3((unsigned)nb), dim3(256), 0, st, bitmap, nw, blocksum, rows_out_dev, cap,
-                     count_out_dev, bad);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
-}
-
-// ---------------------------------------------------------------- several tables in one coalesce (ps_coalesce_tables)
-// A model with T row-sparse tables would pay 3 T launches for its touched lists.  Here the three kernels run ONCE: the mark
-// grid is the concatenation of the tables' index spaces (each rounded up to whole blocks), the count / emit grids the
-// concatenation of their bitmap blocks; a block finds its table in a prefix array of at most four entries that travels
-// by value.  Per table the workspace layout, the status word and the output are ps_coalesce_rows' own.
-#define CO_MAX_TABLES 4
+// ---------------------------------------------------------------- coalesce (ps_coalesce_rows, ps_coalesce_tables)
+// Three launches whatever the number of tables: the mark grid is the concatenation of the tables' index spaces (each rounded
+// up to whole blocks), the count / emit grids the concatenation of their bitmap blocks.  Every table has a workspace, a
+// status word and an output of its own; ps_coalesce_rows is the one-table form.
+struct IdxLists { PsIdxList l[PS_MAX_IDX_LISTS]; int32_t n; int64_t total; };
 struct CoTab {
   IdxLists L;
   int64_t n_rows, pad_row, n_words;
   unsigned long long* bitmap; int32_t* blocksum; int32_t* bad;
   int64_t* rows; int64_t cap; int32_t* count;
 };
-struct CoTabs { CoTab t[CO_MAX_TABLES]; int32_t mblk0[CO_MAX_TABLES + 1]; int32_t blk0[CO_MAX_TABLES + 1]; int32_t n; };
-
-__device__ inline int co_find(const int32_t* blk0, int n, int blk) {
-  int k = 0;
-  while (k < n - 1 && blk >= blk0[k + 1]) ++k;
-  return k;
-}
+struct CoTabs { CoTab t[ROWS_MAX_TABLES]; int32_t mblk0[ROWS_MAX_TABLES + 1]; int32_t blk0[ROWS_MAX_TABLES + 1]; int32_t n; };
 
 __global__ __launch_bounds__(256) void co_mark_tabs_kernel(CoTabs T) {
-  const int t = co_find(T.mblk0, T.n, (int)blockIdx.x);
+  const int t = tab_find(T.mblk0, T.n, (int)blockIdx.x);
   const CoTab& tb = T.t[t];
   // (a table with blocks here has total > 0.)  The id is loaded first, from a clamped position, and judged afterwards: no
   // load sits behind the bounds test
@@ -188,7 +74,7 @@ __global__ __launch_bounds__(256) void co_mark_tabs_kernel(CoTabs T) {
 
 __global__ __launch_bounds__(256) void co_count_tabs_kernel(CoTabs T) {
   __shared__ int sh[4];
-  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const int t = tab_find(T.blk0, T.n, (int)blockIdx.x);
   const CoTab& tb = T.t[t];
   const int lb = (int)blockIdx.x - T.blk0[t];
   const int64_t w0 = (int64_t)lb * CO_WORDS_PER_BLOCK + threadIdx.x;
@@ -203,7 +89,7 @@ __global__ __launch_bounds__(256) void co_count_tabs_kernel(CoTabs T) {
 __global__ __launch_bounds__(256) void co_emit_tabs_kernel(CoTabs T) {
   __shared__ int sh[256];
   __shared__ int base_sh;
-  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const int t = tab_find(T.blk0, T.n, (int)blockIdx.x);
   const CoTab& tb = T.t[t];
   const int lb = (int)blockIdx.x - T.blk0[t];
   const int nb = T.blk0[t + 1] - T.blk0[t];
@@ -244,51 +130,88 @@ __global__ __launch_bounds__(256) void co_emit_tabs_kernel(CoTabs T) {
   if (lb == nb - 1 && threadIdx.x == 255) *tb.count = base + sh[255];
 }
 
+// where a table's bitmap, block sums and status word sit in its workspace, and where its ids go
+static void co_place(CoTab* tb, int64_t n_rows, int64_t pad_row, void* ws, int64_t* rows_out, int64_t cap, int32_t* count_out) {
+  tb->n_rows = n_rows; tb->pad_row = pad_row; tb->n_words = co_words(n_rows);
+  tb->bitmap = (unsigned long long*)ws;
+  tb->blocksum = (int32_t*)(tb->bitmap + tb->n_words);
+  tb->bad = tb->blocksum + co_blocks(n_rows);
+  tb->rows = rows_out; tb->cap = cap; tb->count = count_out;
+}
+
+// one table of a coalesce from what the caller gave, or the refusal (`who` names the entry, and the table where there are several)
+static int co_fill(const char* who, const PsIdxList* lists, int32_t n_lists, int64_t n_rows, int64_t pad_row, void* ws,
+                   int64_t* rows_out, int64_t cap, int32_t* count_out, CoTab* tb) {
+  PS_REQUIRE(lists && n_lists > 0 && n_lists <= PS_MAX_IDX_LISTS, "%s: 1..%d index lists", who, PS_MAX_IDX_LISTS);
+  PS_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 37) && ws && rows_out && count_out && cap > 0, "%s: bad argument", who);
+  tb->L.n = n_lists; tb->L.total = 0;
+  for (int i = 0; i < n_lists; ++i) {
+    PS_REQUIRE(lists[i].n >= 0 && (lists[i].n == 0 || lists[i].idx), "%s: list %d null", who, i);
+    tb->L.l[i] = lists[i];
+    tb->L.total += lists[i].n;
+  }
+  const int64_t need = tb->L.total < n_rows ? tb->L.total : n_rows;
+  PS_REQUIRE(cap >= need, "%s: rows_out capacity %lld < %lld", who, (long long)cap, (long long)need);
+  co_place(tb, n_rows, pad_row, ws, rows_out, cap, count_out);
+  return PS_OK;
+}
+
+// the tables' first blocks in the mark grid (items[t] slots to mark, 256 a block) and in the count / emit grid
+static int co_grids(const char* who, CoTabs* T, const int64_t* items) {
+  int64_t mb = 0, cb = 0;
+  for (int t = 0; t <= ROWS_MAX_TABLES; ++t) {
+    T->mblk0[t] = (int32_t)mb; T->blk0[t] = (int32_t)cb;
+    if (t >= T->n) continue;
+    mb += (items[t] + 255) / 256;
+    cb += co_blocks(T->t[t].n_rows);
+    PS_REQUIRE(mb < ((int64_t)1 << 31) && cb < ((int64_t)1 << 31), "%s: grid too large", who);
+  }
+  return PS_OK;
+}
+
+// mark (`mark`: over the tables' index lists; no launch when there is nothing to mark), count, emit.  tags: the kernel timer's
+static int co_launch(const CoTabs& T, bool mark, const char* count_tag, const char* emit_tag, hipStream_t st) {
+  const unsigned mb = (unsigned)T.mblk0[ROWS_MAX_TABLES], cb = (unsigned)T.blk0[ROWS_MAX_TABLES];
+  if (mark && mb > 0) {
+    hipLaunchKernelGGL(co_mark_tabs_kernel, dim3(mb), dim3(256), 0, st, T);
+    PS_LAUNCH_CHECK();
+  }
+  { KTimeScope kt(count_tag, st); PS_KLAUNCH(co_count_tabs_kernel, dim3(cb), dim3(256), 0, st, T); }
+  PS_LAUNCH_CHECK();
+  { KTimeScope kt(emit_tag, st); PS_KLAUNCH(co_emit_tabs_kernel, dim3(cb), dim3(256), 0, st, T); }
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+extern "C" int ps_coalesce_rows(const PsIdxList* lists_host, int32_t n_lists, int64_t n_rows, int64_t pad_row,
+                                void* ws_dev, int64_t* rows_out_dev, int64_t cap, int32_t* count_out_dev,
+                                ps_stream_t stream) {
+  CoTabs T = CoTabs();
+  T.n = 1;
+  TRY(co_fill("coalesce", lists_host, n_lists, n_rows, pad_row, ws_dev, rows_out_dev, cap, count_out_dev, &T.t[0]));
+  PS_REQUIRE(T.t[0].L.total < ((int64_t)1 << 31), "coalesce: too many indices");
+  TRY(co_grids("coalesce", &T, &T.t[0].L.total));
+  return co_launch(T, true, "coalesce_count", "coalesce_emit", (hipStream_t)stream);
+}
+
 extern "C" int ps_coalesce_tables(const PsCoalesceTable* tabs_host, int32_t n_tabs, ps_stream_t stream) {
-  PS_REQUIRE(tabs_host && n_tabs >= 1 && n_tabs <= CO_MAX_TABLES, "coalesce_tables: 1..%d tables (%d given)", CO_MAX_TABLES,
+  PS_REQUIRE(tabs_host && n_tabs >= 1 && n_tabs <= ROWS_MAX_TABLES, "coalesce_tables: 1..%d tables (%d given)", ROWS_MAX_TABLES,
              (int)n_tabs);
   CoTabs T = CoTabs();
   T.n = n_tabs;
-  int64_t mb = 0, cb = 0, all = 0;
+  int64_t items[ROWS_MAX_TABLES], all = 0;
   for (int t = 0; t < n_tabs; ++t) {
     const PsCoalesceTable& h = tabs_host[t];
-    CoTab& tb = T.t[t];
-    PS_REQUIRE(h.n_lists > 0 && h.n_lists <= PS_MAX_IDX_LISTS, "coalesce_tables: table %d: 1..%d index lists", t, PS_MAX_IDX_LISTS);
-    PS_REQUIRE(h.n_rows > 0 && h.n_rows < ((int64_t)1 << 37) && h.ws_dev && h.rows_out_dev && h.count_out_dev && h.cap > 0,
-               "coalesce_tables: table %d: bad argument", t);
+    char who[40];
+    snprintf(who, sizeof who, "coalesce_tables: table %d", t);
+    TRY(co_fill(who, h.lists, h.n_lists, h.n_rows, h.pad_row, h.ws_dev, h.rows_out_dev, h.cap, h.count_out_dev, &T.t[t]));
     for (int u = 0; u < t; ++u)
       PS_REQUIRE(tabs_host[u].ws_dev != h.ws_dev, "coalesce_tables: tables %d and %d share a workspace", u, t);
-    tb.L.n = h.n_lists; tb.L.total = 0;
-    for (int i = 0; i < h.n_lists; ++i) {
-      PS_REQUIRE(h.lists[i].n >= 0 && (h.lists[i].n == 0 || h.lists[i].idx), "coalesce_tables: table %d: list %d null", t, i);
-      tb.L.l[i] = h.lists[i];
-      tb.L.total += h.lists[i].n;
-    }
-    const int64_t need = tb.L.total < h.n_rows ? tb.L.total : h.n_rows;
-    PS_REQUIRE(h.cap >= need, "coalesce_tables: table %d: rows_out capacity %lld < %lld", t, (long long)h.cap, (long long)need);
-    all += tb.L.total;
+    all += items[t] = T.t[t].L.total;
     PS_REQUIRE(all < ((int64_t)1 << 31), "coalesce_tables: too many indices");
-    tb.n_rows = h.n_rows; tb.pad_row = h.pad_row; tb.n_words = co_words(h.n_rows);
-    tb.bitmap = (unsigned long long*)h.ws_dev;
-    tb.blocksum = (int32_t*)(tb.bitmap + tb.n_words);
-    tb.bad = tb.blocksum + co_blocks(h.n_rows);
-    tb.rows = h.rows_out_dev; tb.cap = h.cap; tb.count = h.count_out_dev;
-    T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb;
-    mb += (tb.L.total + 255) / 256;
-    cb += co_blocks(h.n_rows);
-    PS_REQUIRE(mb < ((int64_t)1 << 31) && cb < ((int64_t)1 << 31), "coalesce_tables: grid too large");
   }
-  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) { T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb; }
-  hipStream_t st = (hipStream_t)stream;
-  if (mb > 0) {
-    hipLaunchKernelGGL(co_mark_tabs_kernel, dim3((unsigned)mb), dim3(256), 0, st, T);
-    PS_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(co_count_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T);
-  PS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(co_emit_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  TRY(co_grids("coalesce_tables", &T, items));
+  return co_launch(T, true, "coalesce_count", "coalesce_emit", (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- gather / scatter of touched rows
@@ -343,97 +266,23 @@ extern "C" const int32_t* ps_coalesce_bad_flag(void* ws_dev, int64_t n_rows) {
   return (const int32_t*)(bitmap + co_words(n_rows)) + co_blocks(n_rows);
 }
 
-// ---------------------------------------------------------------- data-parallel exchange of touched rows
-// One rank's wire format for one table: msg_rows[u] = row id (u < count, ascending) or -1 (u >= count), and
-// msg_vals[u, :] = its gradient row (zeros past count, so the bytes on the wire are a function of the gradient only).
-// Fixed capacity `cap` (the step's index count, a function of the batch SHAPE): no size ever crosses to the host.
-__global__ __launch_bounds__(256) void rows_pack_kernel(const float* grad, const int64_t* rows, const int32_t* count,
-                                                        int64_t cap, int64_t* msg_rows, float* msg_vals, int d) {
-  const int64_t n = (int64_t)*count;
-  const int64_t u = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
-  if (u >= cap) return;
-  const int lane = threadIdx.x & 31;
-  const bool live = u < n;
-  const int64_t r = live ? rows[u] : -1;
-  if (lane == 0) msg_rows[u] = r;
-  const float4* g4 = (const float4*)(grad + (live ? r : 0) * (int64_t)d);
-  float4* v4 = (float4*)(msg_vals + u * (int64_t)d);
-  for (int j = lane; j < d / 4; j += 32) v4[j] = live ? g4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-extern "C" int ps_pack_rows(const float* grad_dev, int32_t d, const int64_t* rows_dev, const int32_t* count_dev,
-                            int64_t cap, int64_t* msg_rows_dev, float* msg_vals_dev, ps_stream_t stream) {
-  PS_REQUIRE(grad_dev && rows_dev && count_dev && msg_rows_dev && msg_vals_dev && cap > 0 && d > 0 && d % 4 == 0,
-             "pack_rows: bad argument");
-  PS_REQUIRE(((((uintptr_t)grad_dev) | ((uintptr_t)msg_vals_dev)) & 15) == 0, "pack_rows: 16-byte alignment");
-  hipLaunchKernelGGL(rows_pack_kernel, dim3((unsigned)((cap + 7) / 8)), dim3(256), 0, (hipStream_t)stream, grad_dev,
-                     rows_dev, count_dev, cap, msg_rows_dev, msg_vals_dev, d);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
-}
-
-// grad[u_rows[u], :] = sum over ranks r = 0 .. world-1, IN RANK ORDER, of the row rank r sent for that id (if any):
-// every rank computes bit-identical sums from the same all-gathered messages, so the replicas stay in lock step.
-// 32 lanes per union row: lane r < world binary-searches rank r's sorted id list, then all lanes add the found rows.
+// ---------------------------------------------------------------- data-parallel exchange of touched rows (ps_pack_*, ps_union_tables, ps_merge_*)
+// One rank's wire format for one table: an id section — ids[u] = row id (u < count, ascending) or -1 (u >= count) — and a
+// value section — vals[u, :] = its gradient row (zeros past count, so the bytes on the wire are a function of the gradient
+// only).  Fixed capacity `cap` (the step's index count, a function of the batch SHAPE): no size ever crosses to the host.
+// One pack kernel and one merge kernel serve both forms of the exchange; a table tells them where its sections are:
+//   ps_pack_rows / ps_merge_rows   one table, the two sections in buffers of their own (rank r's at r * cap ids / rows)
+//   ps_*_tables                    every table of a model in ONE byte buffer per rank — the id sections of all tables, then
+//                                  their value sections, every section on a 16-byte boundary, the total a multiple of 16 — so
+//                                  one all-gather moves it, and pack / union / merge run once each over all tables: the pack
+//                                  and merge grids are the concatenation of the tables' row blocks, the union's mark grid that
+//                                  of the gathered id slots.  The union's count and emit stages are the coalesce kernels.
 #define PS_MERGE_MAX_WORLD 32
-__global__ __launch_bounds__(256) void rows_merge_kernel(const int64_t* all_rows, const float* all_vals, int world,
-                                                         int64_t cap, int d, float* grad, const int64_t* u_rows,
-                                                         const int32_t* u_count) {
-  const int64_t u = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
-  const int lane = threadIdx.x & 31;
-  const bool live = u < (int64_t)*u_count;          // uniform per 32-lane group
-  int64_t found = -1;
-  const int64_t row = live ? u_rows[u] : -1;
-  if (live && lane < world) {
-    const int64_t* lst = all_rows + (size_t)lane * cap;   // ascending ids, then -1 padding (= +infinity here)
-    int64_t lo = 0, hi = cap;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      const int64_t v = lst[mid];
-      if (v >= 0 && v < row) lo = mid + 1; else hi = mid;
-    }
-    if (lo < cap && lst[lo] == row) found = lo;
-  }
-  if (!live) return;
-  float4* g4 = (float4*)(grad + row * (int64_t)d);
-  for (int j = lane; j < d / 4; j += 32) {
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < world; ++r) {
-      const int64_t pos = __shfl(found, (threadIdx.x & 32) + r, 64);
-      if (pos >= 0) {
-        const float4 x = ((const float4*)(all_vals + ((size_t)r * cap + pos) * d))[j];
-        acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
-      }
-    }
-    g4[j] = acc;
-  }
-}
-
-extern "C" int ps_merge_rows(const int64_t* all_rows_dev, const float* all_vals_dev, int32_t world, int64_t cap,
-                             int32_t d, float* grad_dev, const int64_t* union_rows_dev, const int32_t* union_count_dev,
-                             int64_t union_cap, ps_stream_t stream) {
-  PS_REQUIRE(all_rows_dev && all_vals_dev && grad_dev && union_rows_dev && union_count_dev, "merge_rows: null argument");
-  PS_REQUIRE(world > 0 && world <= PS_MERGE_MAX_WORLD && cap > 0 && union_cap > 0 && d > 0 && d % 4 == 0,
-             "merge_rows: world %d (<= %d), cap %lld, d %d", world, PS_MERGE_MAX_WORLD, (long long)cap, d);
-  PS_REQUIRE(((((uintptr_t)grad_dev) | ((uintptr_t)all_vals_dev)) & 15) == 0, "merge_rows: 16-byte alignment");
-  hipLaunchKernelGGL(rows_merge_kernel, dim3((unsigned)((union_cap + 7) / 8)), dim3(256), 0, (hipStream_t)stream,
-                     all_rows_dev, all_vals_dev, world, cap, d, grad_dev, union_rows_dev, union_count_dev);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
-}
-
-// ---------------------------------------------------------------- every table's rows in ONE message (ps_*_tables)
-// A model with T row-sparse tables would pay, table by table, 2 T all-gathers and 5 T launches for its exchange.  Here a
-// rank's message is ONE byte buffer — the id sections of all tables (cap_t int64 each: ascending touched ids, then -1), then
-// their value sections (cap_t x d_t fp32: the gradient rows, then zeros), every section on a 16-byte boundary, the total a
-// multiple of 16 — so one all-gather moves it, and pack / union / merge run once each over all tables: the pack and merge grids
-// are the concatenation of the tables' row blocks, the union's mark grid that of the gathered id slots; a block finds its table
-// in a prefix array that travels by value (co_find).  The union's count and emit stages are the coalesce kernels themselves.
-struct RowMsgLayout { int64_t ids_off[CO_MAX_TABLES], vals_off[CO_MAX_TABLES], bytes; };
+struct RowMsgLayout { int64_t ids_off[ROWS_MAX_TABLES], vals_off[ROWS_MAX_TABLES], bytes; };
 
 static int row_msg_layout(const char* who, const int64_t* caps, const int32_t* ds, int32_t n_tabs, RowMsgLayout* L) {
   PS_REQUIRE(caps && ds, "%s: null argument", who);
-  PS_REQUIRE(n_tabs >= 1 && n_tabs <= CO_MAX_TABLES, "%s: 1..%d tables (%d given)", who, CO_MAX_TABLES, (int)n_tabs);
+  PS_REQUIRE(n_tabs >= 1 && n_tabs <= ROWS_MAX_TABLES, "%s: 1..%d tables (%d given)", who, ROWS_MAX_TABLES, (int)n_tabs);
   int64_t off = 0;
   for (int t = 0; t < n_tabs; ++t) {
     PS_REQUIRE(caps[t] > 0 && caps[t] < ((int64_t)1 << 31), "%s: table %d: capacity %lld", who, t, (long long)caps[t]);
@@ -463,10 +312,10 @@ extern "C" int64_t ps_row_msg_layout(const int64_t* caps_host, const int32_t* ds
 // what the three entries check alike: the table count, the layout the tables' (cap, d) give against the caller's msg_bytes
 static int row_msg_check(const char* who, const PsRowMsgTable* tabs, int32_t n_tabs, const void* buf, int64_t msg_bytes,
                          RowMsgLayout* L) {
-  PS_REQUIRE(tabs && n_tabs >= 1 && n_tabs <= CO_MAX_TABLES, "%s: 1..%d tables (%d given)", who, CO_MAX_TABLES, (int)n_tabs);
+  PS_REQUIRE(tabs && n_tabs >= 1 && n_tabs <= ROWS_MAX_TABLES, "%s: 1..%d tables (%d given)", who, ROWS_MAX_TABLES, (int)n_tabs);
   PS_REQUIRE(buf, "%s: null message buffer", who);
   PS_REQUIRE((((uintptr_t)buf) & 15) == 0, "%s: message buffer not 16-byte aligned", who);
-  int64_t caps[CO_MAX_TABLES]; int32_t ds[CO_MAX_TABLES];
+  int64_t caps[ROWS_MAX_TABLES]; int32_t ds[ROWS_MAX_TABLES];
   for (int t = 0; t < n_tabs; ++t) { caps[t] = tabs[t].cap; ds[t] = tabs[t].d; }
   TRY(row_msg_layout(who, caps, ds, n_tabs, L));                  // (capacities 1 .. 2^31 - 1, widths a multiple of 4)
   PS_REQUIRE(msg_bytes == L->bytes, "%s: msg_bytes %lld, the tables' layout has %lld", who, (long long)msg_bytes, (long long)L->bytes);
@@ -481,15 +330,16 @@ struct PackTab {
   const float* grad; const int64_t* rows; const int32_t* count;
   int64_t cap, list_cap, n_rows;
   int64_t* ids; float* vals; int32_t d;
+  int32_t tail;                 // the id section is rounded up to 16 bytes: an odd cap writes ids[cap] = -1 too
 };
-struct PackTabs { PackTab t[CO_MAX_TABLES]; int32_t blk0[CO_MAX_TABLES + 1]; int32_t n; };
+struct PackTabs { PackTab t[ROWS_MAX_TABLES]; int32_t blk0[ROWS_MAX_TABLES + 1]; int32_t n; };
 
-// rows_pack_kernel's message, every table in one launch: 32 lanes per slot, 16 B per lane, 8 slots per block.  The row id is
+// One rank's message: 32 lanes per slot, 16 B per lane, 8 slots per block.  The row id is
 // loaded from a clamped position of the list and the gradient row from a clamped row, both judged afterwards: no vector load
 // sits behind the bounds test.  A slot past the list's count (or holding an id outside the table, which a
 // coalesced list never does) is written as -1 / zeros, whatever the buffer held: the bytes are a function of the gradient only.
 __global__ __launch_bounds__(256) void rows_pack_tabs_kernel(PackTabs T) {
-  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const int t = tab_find(T.blk0, T.n, (int)blockIdx.x);
   const PackTab& tb = T.t[t];
   const int64_t u = (int64_t)((int)blockIdx.x - T.blk0[t]) * 8 + (threadIdx.x >> 5);
   const int lane = threadIdx.x & 31;
@@ -505,7 +355,36 @@ __global__ __launch_bounds__(256) void rows_pack_tabs_kernel(PackTabs T) {
     if (slot) v4[j] = live ? g : zero;
   }
   if (slot && lane == 0) tb.ids[u] = live ? r0 : -1;
-  if (lane == 1 && u == tb.cap - 1 && (tb.cap & 1)) tb.ids[tb.cap] = -1;     // the 8 bytes that round an odd section up to 16
+  if (tb.tail && lane == 1 && u == tb.cap - 1 && (tb.cap & 1)) tb.ids[tb.cap] = -1;
+}
+
+static int pack_launch(const char* who, PackTabs& T, hipStream_t st) {
+  int64_t b = 0;
+  for (int t = 0; t <= ROWS_MAX_TABLES; ++t) {
+    T.blk0[t] = (int32_t)b;
+    if (t < T.n) b += (T.t[t].cap + 7) / 8;                   // (cap < 2^31 each: at most 2^30 blocks)
+  }
+  KTimeScope kt(who, st);
+  PS_KLAUNCH(rows_pack_tabs_kernel, dim3((unsigned)b), dim3(256), 0, st, T);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+extern "C" int ps_pack_rows(const float* grad_dev, int32_t d, int64_t n_rows, const int64_t* rows_dev, const int32_t* count_dev,
+                            int64_t list_cap, int64_t cap, int64_t* msg_rows_dev, float* msg_vals_dev, ps_stream_t stream) {
+  PS_REQUIRE(grad_dev && rows_dev && count_dev && msg_rows_dev && msg_vals_dev, "pack_rows: null argument");
+  PS_REQUIRE(cap > 0 && cap < ((int64_t)1 << 31) && d > 0 && d % 4 == 0, "pack_rows: capacity %lld, width %d", (long long)cap, (int)d);
+  PS_REQUIRE(n_rows > 0, "pack_rows: n_rows %lld", (long long)n_rows);
+  PS_REQUIRE(list_cap > 0 && list_cap <= cap, "pack_rows: list capacity %lld, message capacity %lld", (long long)list_cap,
+             (long long)cap);
+  PS_REQUIRE(((((uintptr_t)grad_dev) | ((uintptr_t)msg_vals_dev)) & 15) == 0, "pack_rows: 16-byte alignment");
+  PackTabs T = PackTabs();
+  T.n = 1;
+  PackTab& tb = T.t[0];
+  tb.grad = grad_dev; tb.rows = rows_dev; tb.count = count_dev;
+  tb.cap = cap; tb.list_cap = list_cap; tb.n_rows = n_rows; tb.d = d;
+  tb.ids = msg_rows_dev; tb.vals = msg_vals_dev;              // (tail 0: msg_rows has cap entries, whatever cap's parity)
+  return pack_launch("pack_rows", T, (hipStream_t)stream);
 }
 
 extern "C" int ps_pack_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, void* msg_dev, int64_t msg_bytes,
@@ -514,7 +393,6 @@ extern "C" int ps_pack_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, vo
   TRY(row_msg_check("pack_tables", tabs_host, n_tabs, msg_dev, msg_bytes, &L));
   PackTabs T = PackTabs();
   T.n = n_tabs;
-  int64_t b = 0;
   for (int t = 0; t < n_tabs; ++t) {
     const PsRowMsgTable& h = tabs_host[t];
     PS_REQUIRE(h.grad_dev && h.rows_dev && h.count_dev, "pack_tables: table %d: null pointer", t);
@@ -527,25 +405,19 @@ extern "C" int ps_pack_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, vo
     tb.cap = h.cap; tb.list_cap = h.list_cap; tb.n_rows = h.n_rows; tb.d = h.d;
     tb.ids = (int64_t*)((char*)msg_dev + L.ids_off[t]);
     tb.vals = (float*)((char*)msg_dev + L.vals_off[t]);
-    T.blk0[t] = (int32_t)b;
-    b += (h.cap + 7) / 8;                                     // (cap < 2^31 each: at most 2^30 blocks)
+    tb.tail = 1;
   }
-  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) T.blk0[t] = (int32_t)b;
-  hipStream_t st = (hipStream_t)stream;
-  KTimeScope kt("pack_tables", st);
-  PS_KLAUNCH(rows_pack_tabs_kernel, dim3((unsigned)b), dim3(256), 0, st, T);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  return pack_launch("pack_tables", T, (hipStream_t)stream);
 }
 
 // the union's mark stage over strided segments: slot i of table t is id u = i % cap of rank r = i / cap, at
 // base + r * stride (bytes) + 8 u; -1 is the pad.  co_mark_tabs_kernel's discipline: the id is loaded from a clamped slot, the
 // bitmap word from a clamped row, and both are judged afterwards.  The bitmaps, block sums, status words and outputs sit in
 // the CoTabs the count and emit kernels take (its index lists stay empty: the segments are not index lists).
-struct CoSegs { const char* base[CO_MAX_TABLES]; int64_t cap[CO_MAX_TABLES]; int64_t total[CO_MAX_TABLES]; int64_t stride; };
+struct CoSegs { const char* base[ROWS_MAX_TABLES]; int64_t cap[ROWS_MAX_TABLES]; int64_t total[ROWS_MAX_TABLES]; int64_t stride; };
 
 __global__ __launch_bounds__(256) void co_mark_segs_kernel(CoTabs T, CoSegs S) {
-  const int t = co_find(T.mblk0, T.n, (int)blockIdx.x);
+  const int t = tab_find(T.mblk0, T.n, (int)blockIdx.x);
   const CoTab& tb = T.t[t];
   const int64_t i0 = (int64_t)((int)blockIdx.x - T.mblk0[t]) * 256 + threadIdx.x;
   const int64_t i = i0 < S.total[t] ? i0 : S.total[t] - 1;
@@ -570,50 +442,38 @@ extern "C" int ps_union_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, c
   CoSegs S = CoSegs();
   T.n = n_tabs;
   S.stride = msg_bytes;
-  int64_t mb = 0, cb = 0;
   for (int t = 0; t < n_tabs; ++t) {
     const PsRowMsgTable& h = tabs_host[t];
-    CoTab& tb = T.t[t];
     PS_REQUIRE(h.ws_dev && h.union_rows_dev && h.union_count_dev, "union_tables: table %d: null pointer", t);
     PS_REQUIRE(h.n_rows > 0 && h.n_rows < ((int64_t)1 << 37), "union_tables: table %d: n_rows %lld", t, (long long)h.n_rows);
     PS_REQUIRE(h.union_cap > 0, "union_tables: table %d: union capacity %lld", t, (long long)h.union_cap);
     for (int u = 0; u < t; ++u)
       PS_REQUIRE(tabs_host[u].ws_dev != h.ws_dev, "union_tables: tables %d and %d share a workspace", u, t);
-    tb.L.n = 0; tb.L.total = 0;
-    tb.n_rows = h.n_rows; tb.pad_row = -1; tb.n_words = co_words(h.n_rows);
-    tb.bitmap = (unsigned long long*)h.ws_dev;
-    tb.blocksum = (int32_t*)(tb.bitmap + tb.n_words);
-    tb.bad = tb.blocksum + co_blocks(h.n_rows);
-    tb.rows = h.union_rows_dev; tb.cap = h.union_cap; tb.count = h.union_count_dev;
+    co_place(&T.t[t], h.n_rows, -1, h.ws_dev, h.union_rows_dev, h.union_cap, h.union_count_dev);
     S.base[t] = (const char*)all_dev + L.ids_off[t];
     S.cap[t] = h.cap; S.total[t] = (int64_t)world * h.cap;
     PS_REQUIRE(S.total[t] < ((int64_t)1 << 31), "union_tables: table %d: too many id slots", t);
-    T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb;
-    mb += (S.total[t] + 255) / 256;                           // (< 2^23 blocks a table, and so is the next line's)
-    cb += co_blocks(h.n_rows);
   }
-  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) { T.mblk0[t] = (int32_t)mb; T.blk0[t] = (int32_t)cb; }
+  TRY(co_grids("union_tables", &T, S.total));                 // (< 2^23 mark blocks a table, and as many count / emit blocks)
   hipStream_t st = (hipStream_t)stream;
-  { KTimeScope kt("union_mark", st); PS_KLAUNCH(co_mark_segs_kernel, dim3((unsigned)mb), dim3(256), 0, st, T, S); }
+  { KTimeScope kt("union_mark", st); PS_KLAUNCH(co_mark_segs_kernel, dim3((unsigned)T.mblk0[ROWS_MAX_TABLES]), dim3(256), 0, st, T, S); }
   PS_LAUNCH_CHECK();
-  { KTimeScope kt("union_count", st); PS_KLAUNCH(co_count_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T); }
-  PS_LAUNCH_CHECK();
-  { KTimeScope kt("union_emit", st); PS_KLAUNCH(co_emit_tabs_kernel, dim3((unsigned)cb), dim3(256), 0, st, T); }
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  return co_launch(T, false, "union_count", "union_emit", st);
 }
 
-// rows_merge_kernel over all tables: per union row, lane r < world binary-searches rank r's id section, then all 32 lanes add
-// the found rows in rank order 0 .. world-1 — the same addends in the same order as ps_merge_rows, on every rank.
+// grad[u_rows[u], :] = sum over ranks r = 0 .. world-1, IN RANK ORDER, of the row rank r sent for that id (if any):
+// every rank computes bit-identical sums from the same all-gathered messages, so the replicas stay in lock step.
+// 32 lanes per union row: lane r < world binary-searches rank r's sorted id section, then all lanes add the found rows.
 struct MergeTab {
-  const char* ids; const char* vals;            // rank 0's sections; rank r's are `stride` bytes further each
+  const char* ids; const char* vals;            // rank 0's sections; rank r's are ids_stride / vals_stride bytes further each
+  int64_t ids_stride, vals_stride;
   int64_t cap, union_cap; int32_t d;
   float* grad; const int64_t* u_rows; const int32_t* u_count;
 };
-struct MergeTabs { MergeTab t[CO_MAX_TABLES]; int32_t blk0[CO_MAX_TABLES + 1]; int32_t n; int32_t world; int64_t stride; };
+struct MergeTabs { MergeTab t[ROWS_MAX_TABLES]; int32_t blk0[ROWS_MAX_TABLES + 1]; int32_t n; int32_t world; };
 
 __global__ __launch_bounds__(256) void rows_merge_tabs_kernel(MergeTabs T) {
-  const int t = co_find(T.blk0, T.n, (int)blockIdx.x);
+  const int t = tab_find(T.blk0, T.n, (int)blockIdx.x);
   const MergeTab& tb = T.t[t];
   const int64_t u = (int64_t)((int)blockIdx.x - T.blk0[t]) * 8 + (threadIdx.x >> 5);
   const int lane = threadIdx.x & 31;
@@ -624,7 +484,7 @@ __global__ __launch_bounds__(256) void rows_merge_tabs_kernel(MergeTabs T) {
   int64_t found = -1;
   const int64_t row = live ? tb.u_rows[u] : -1;
   if (live && lane < T.world) {
-    const int64_t* lst = (const int64_t*)(tb.ids + (size_t)lane * T.stride);   // ascending ids, then -1 padding (= +infinity here)
+    const int64_t* lst = (const int64_t*)(tb.ids + (size_t)lane * tb.ids_stride);   // ascending ids, then -1 padding (= +infinity here)
     int64_t lo = 0, hi = cap;
     while (lo < hi) {
       const int64_t mid = (lo + hi) >> 1;
@@ -644,12 +504,43 @@ __global__ __launch_bounds__(256) void rows_merge_tabs_kernel(MergeTabs T) {
     for (int r = 0; r < T.world; ++r) {
       const int64_t pos = __shfl(found, (threadIdx.x & 32) + r, 64);
       if (pos >= 0 && mine) {
-        const float4 x = ((const float4*)(tb.vals + (size_t)r * T.stride + (size_t)pos * d * 4))[j];
+        const float4 x = ((const float4*)(tb.vals + (size_t)r * tb.vals_stride + (size_t)pos * d * 4))[j];
         acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
       }
     }
     if (mine) g4[j] = acc;
   }
+}
+
+static int merge_launch(const char* who, MergeTabs& T, hipStream_t st) {
+  int64_t b = 0;
+  for (int t = 0; t <= ROWS_MAX_TABLES; ++t) {
+    T.blk0[t] = (int32_t)b;
+    if (t < T.n) b += (T.t[t].union_cap + 7) / 8;
+    PS_REQUIRE(b < ((int64_t)1 << 31), "%s: grid too large", who);
+  }
+  KTimeScope kt(who, st);
+  PS_KLAUNCH(rows_merge_tabs_kernel, dim3((unsigned)b), dim3(256), 0, st, T);
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// one table, the ranks' id lists in all_rows [world, cap] and their rows in all_vals [world, cap, d]
+extern "C" int ps_merge_rows(const int64_t* all_rows_dev, const float* all_vals_dev, int32_t world, int64_t cap,
+                             int32_t d, float* grad_dev, const int64_t* union_rows_dev, const int32_t* union_count_dev,
+                             int64_t union_cap, ps_stream_t stream) {
+  PS_REQUIRE(all_rows_dev && all_vals_dev && grad_dev && union_rows_dev && union_count_dev, "merge_rows: null argument");
+  PS_REQUIRE(world > 0 && world <= PS_MERGE_MAX_WORLD && cap > 0 && union_cap > 0 && d > 0 && d % 4 == 0,
+             "merge_rows: world %d (<= %d), cap %lld, d %d", world, PS_MERGE_MAX_WORLD, (long long)cap, d);
+  PS_REQUIRE(((((uintptr_t)grad_dev) | ((uintptr_t)all_vals_dev)) & 15) == 0, "merge_rows: 16-byte alignment");
+  MergeTabs T = MergeTabs();
+  T.n = 1; T.world = world;
+  MergeTab& tb = T.t[0];
+  tb.ids = (const char*)all_rows_dev; tb.vals = (const char*)all_vals_dev;
+  tb.ids_stride = cap * 8; tb.vals_stride = cap * (int64_t)d * 4;
+  tb.cap = cap; tb.union_cap = union_cap; tb.d = d;
+  tb.grad = grad_dev; tb.u_rows = union_rows_dev; tb.u_count = union_count_dev;
+  return merge_launch("merge_rows", T, (hipStream_t)stream);
 }
 
 extern "C" int ps_merge_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, const void* all_dev, int64_t msg_bytes,
@@ -658,8 +549,7 @@ extern "C" int ps_merge_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, c
   TRY(row_msg_check("merge_tables", tabs_host, n_tabs, all_dev, msg_bytes, &L));
   TRY(row_msg_world("merge_tables", world));
   MergeTabs T = MergeTabs();
-  T.n = n_tabs; T.world = world; T.stride = msg_bytes;
-  int64_t b = 0;
+  T.n = n_tabs; T.world = world;
   for (int t = 0; t < n_tabs; ++t) {
     const PsRowMsgTable& h = tabs_host[t];
     PS_REQUIRE(h.grad_dev && h.union_rows_dev && h.union_count_dev, "merge_tables: table %d: null pointer", t);
@@ -667,31 +557,16 @@ extern "C" int ps_merge_tables(const PsRowMsgTable* tabs_host, int32_t n_tabs, c
     PS_REQUIRE(h.union_cap > 0, "merge_tables: table %d: union capacity %lld", t, (long long)h.union_cap);
     MergeTab& tb = T.t[t];
     tb.ids = (const char*)all_dev + L.ids_off[t]; tb.vals = (const char*)all_dev + L.vals_off[t];
+    tb.ids_stride = tb.vals_stride = msg_bytes;
     tb.cap = h.cap; tb.union_cap = h.union_cap; tb.d = h.d;
     tb.grad = h.grad_dev; tb.u_rows = h.union_rows_dev; tb.u_count = h.union_count_dev;
-    T.blk0[t] = (int32_t)b;
-    b += (h.union_cap + 7) / 8;
-    PS_REQUIRE(b < ((int64_t)1 << 31), "merge_tables: grid too large");
   }
-  for (int t = n_tabs; t <= CO_MAX_TABLES; ++t) T.blk0[t] = (int32_t)b;
-  hipStream_t st = (hipStream_t)stream;
-  KTimeScope kt("merge_tables", st);
-  PS_KLAUNCH(rows_merge_tabs_kernel, dim3((unsigned)b), dim3(256), 0, st, T);
-  PS_LAUNCH_CHECK();
-  return PS_OK;
+  return merge_launch("merge_tables", T, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- row-sparse clip + Adam
-#define RS_MAX_TABLES 4
-
 #define RS_ROWS_PER_BLOCK 8
-struct RowTables { PsRowTable t[RS_MAX_TABLES]; int32_t blk0[RS_MAX_TABLES + 1]; int32_t n; };
-
-__device__ inline int rs_find(const RowTables& T, int blk) {
-  int k = 0;
-  while (k < T.n - 1 && blk >= T.blk0[k + 1]) ++k;
-  return k;
-}
+struct RowTables { PsRowTable t[ROWS_MAX_TABLES]; int32_t blk0[ROWS_MAX_TABLES + 1]; int32_t n; };
 
 // grid = n_chunks dense chunks, then the row blocks of every table.  partial[block] = its sum of squares.
 __global__ __launch_bounds__(256) void rs_sumsq_kernel(const char* plan, int n_chunks, RowTables T, float grad_scale,
@@ -702,7 +577,7 @@ __global__ __launch_bounds__(256) void rs_sumsq_kernel(const char* plan, int n_c
   if (blk < n_chunks) {
     s = adam_sumsq_chunk(plan, blk, grad_scale, sh);
   } else {
-    const int k = rs_find(T, blk - n_chunks);
+    const int k = tab_find(T.blk0, T.n, blk - n_chunks);
     const PsRowTable& tb = T.t[k];
     const int64_t u = (int64_t)(blk - n_chunks - T.blk0[k]) * RS_ROWS_PER_BLOCK + (threadIdx.x >> 5);
     const int64_t n = *tb.count;
@@ -746,7 +621,7 @@ __global__ __launch_bounds__(256) void rs_update_kernel(const char* plan, int n_
   const AdamScal a = {scal[0], scal[1], scal[2], hp.beta1, hp.beta2, hp.eps, hp.weight_decay, 0, scal[3], hp.method};
   const int blk = blockIdx.x;
   if (blk < n_chunks) { adam_update_chunk(plan, blk, a); return; }
-  const int k = rs_find(T, blk - n_chunks);
+  const int k = tab_find(T.blk0, T.n, blk - n_chunks);
   const PsRowTable& tb = T.t[k];
   const int64_t u = (int64_t)(blk - n_chunks - T.blk0[k]) * RS_ROWS_PER_BLOCK + (threadIdx.x >> 5);
   if (u >= (int64_t)*tb.count) return;
@@ -763,7 +638,7 @@ __global__ __launch_bounds__(256) void rs_update_kernel(const char* plan, int n_
 }
 
 static int rs_pack(const PsRowTable* tabs, int32_t n_tables, RowTables* T) {
-  PS_REQUIRE(n_tables >= 0 && n_tables <= RS_MAX_TABLES && (n_tables == 0 || tabs), "rowsparse: 0..%d tables", RS_MAX_TABLES);
+  PS_REQUIRE(n_tables >= 0 && n_tables <= ROWS_MAX_TABLES && (n_tables == 0 || tabs), "rowsparse: 0..%d tables", ROWS_MAX_TABLES);
   T->n = n_tables;
   int64_t b = 0;
   for (int i = 0; i < n_tables; ++i) {
@@ -777,7 +652,7 @@ static int rs_pack(const PsRowTable* tabs, int32_t n_tables, RowTables* T) {
     b += (t.cap + RS_ROWS_PER_BLOCK - 1) / RS_ROWS_PER_BLOCK;
     PS_REQUIRE(b < (1 << 30), "rowsparse: too many rows");
   }
-  for (int i = n_tables; i <= RS_MAX_TABLES; ++i) T->blk0[i] = (int32_t)b;
+  for (int i = n_tables; i <= ROWS_MAX_TABLES; ++i) T->blk0[i] = (int32_t)b;
   return PS_OK;
 }
 
@@ -785,7 +660,7 @@ static int rs_pack(const PsRowTable* tabs, int32_t n_tables, RowTables* T) {
 extern "C" int64_t ps_adam_rowsparse_state_floats(int32_t n_chunks, const PsRowTable* tables_host, int32_t n_tables) {
   RowTables T;
   if (rs_pack(tables_host, n_tables, &T) != PS_OK) return -1;
-  return 4 + (int64_t)n_chunks + T.blk0[RS_MAX_TABLES];
+  return 4 + (int64_t)n_chunks + T.blk0[ROWS_MAX_TABLES];
 }
 
 extern "C" int ps_clip_adam_rowsparse(const void* plan_dev, int32_t n_chunks, const PsRowTable* tables_host,
@@ -796,7 +671,7 @@ extern "C" int ps_clip_adam_rowsparse(const void* plan_dev, int32_t n_chunks, co
   RowTables T;
   int rc = rs_pack(tables_host, n_tables, &T);
   if (rc != PS_OK) return rc;
-  const int n_blocks = n_chunks + T.blk0[RS_MAX_TABLES];
+  const int n_blocks = n_chunks + T.blk0[ROWS_MAX_TABLES];
   PS_REQUIRE(n_blocks > 0, "clip_adam_rowsparse: nothing to update");
   hipStream_t st = (hipStream_t)stream;
   float* scal = (float*)(state_dev + 2);
@@ -827,7 +702,7 @@ extern "C" int ps_clip_adam_rowsparse(const void* plan_dev, int32_t n_chunks, co
 // later steps cannot change it either — except for an element so small that a larger later step size could reach it, which
 // keeps the loop going (|p| < 1e-20 with m != 0).  Cost: the replay is sequential per row, up to ~1e5 steps for a row that
 // was last touched long ago — an exactness mode for pinning the optimizer, not the fast path.
-struct CatchTables { PsRowTable t[RS_MAX_TABLES]; int32_t* last[RS_MAX_TABLES]; int64_t n_rows[RS_MAX_TABLES]; int64_t wave0[RS_MAX_TABLES + 1]; int32_t n; };
+struct CatchTables { PsRowTable t[ROWS_MAX_TABLES]; int32_t* last[ROWS_MAX_TABLES]; int64_t n_rows[ROWS_MAX_TABLES]; int64_t wave0[ROWS_MAX_TABLES + 1]; int32_t n; };
 template <int NK>
 __device__ inline void catchup_row(const PsRowTable& tb, int32_t* last, int64_t row, const PsAdamHyper& hp, int64_t T, int advance,
                                    float gzero, int lane) {
@@ -887,7 +762,7 @@ __global__ __launch_bounds__(256) void rs_catchup_kernel(CatchTables C, const Ps
 extern "C" int ps_rowsparse_catchup(const PsRowTable* tables_host, int32_t n_tables, int32_t* const* last_dev,
                                     const int64_t* n_rows_host, const PsAdamHyper* hyper, const int64_t* state_dev,
                                     int32_t advance, int32_t all_rows, ps_stream_t stream) {
-  PS_REQUIRE(tables_host && last_dev && n_rows_host && hyper && state_dev && n_tables >= 1 && n_tables <= RS_MAX_TABLES,
+  PS_REQUIRE(tables_host && last_dev && n_rows_host && hyper && state_dev && n_tables >= 1 && n_tables <= ROWS_MAX_TABLES,
              "rowsparse_catchup: bad argument");
   CatchTables C = CatchTables();
   C.n = n_tables;
@@ -900,7 +775,7 @@ extern "C" int ps_rowsparse_catchup(const PsRowTable* tables_host, int32_t n_tab
     C.wave0[i] = w;
     w += all_rows ? n_rows_host[i] : t.cap;
   }
-  for (int i = n_tables; i <= RS_MAX_TABLES; ++i) C.wave0[i] = w;
+  for (int i = n_tables; i <= ROWS_MAX_TABLES; ++i) C.wave0[i] = w;
   if (w == 0) return PS_OK;
   PS_REQUIRE((w + 3) / 4 < ((int64_t)1 << 31), "rowsparse_catchup: too many rows");
   hipLaunchKernelGGL(rs_catchup_kernel, dim3((unsigned)((w + 3) / 4)), dim3(256), 0, (hipStream_t)stream, C, *hyper, state_dev,
@@ -1027,7 +902,7 @@ extern "C" int ps_rowsparse_sumsq(const void* plan_dev, int32_t n_chunks, const 
   RowTables T;
   int rc = rs_pack(tables_host, n_tables, &T);
   if (rc != PS_OK) return rc;
-  const int n_blocks = n_chunks + T.blk0[RS_MAX_TABLES];
+  const int n_blocks = n_chunks + T.blk0[ROWS_MAX_TABLES];
   PS_REQUIRE(n_blocks > 0, "rowsparse_sumsq: nothing to update");
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)(state_dev + 2) + 4;
@@ -1046,7 +921,7 @@ extern "C" int ps_rowsparse_update_ext(const void* plan_dev, int32_t n_chunks, c
   RowTables T;
   int rc = rs_pack(tables_host, n_tables, &T);
   if (rc != PS_OK) return rc;
-  const int n_blocks = n_chunks + T.blk0[RS_MAX_TABLES];
+  const int n_blocks = n_chunks + T.blk0[ROWS_MAX_TABLES];
   PS_REQUIRE(n_blocks > 0, "rowsparse_update_ext: nothing to update");
   hipStream_t st = (hipStream_t)stream;
   float* scal = (float*)(state_dev + 2);

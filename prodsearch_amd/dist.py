@@ -124,7 +124,53 @@ def _all_gather_flat(out, inp, world, group, flat=True):
         dist.all_gather([out[r].view(-1) for r in range(world)], inp.view(-1), group=group)
 
 
-class SparseGradExchange(object):
+class _RowExchange(object):
+    """What the two row exchanges below share; the protocol — which collectives, over what — is each subclass's own."""
+
+    _OVER_CAPACITY = None        # the refusal's text: %(local)d rows addressed, %(table)s, %(cap)d rows agreed
+
+    def __init__(self, model, optim=None, group=None):
+        self.model = model
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self._flat = _flat_gather_supported(group) if self.world > 1 else True
+        if optim is not None:
+            optim.grad_scale = 1.0 / self.world
+
+    def _check_capacity(self, local, cap, path):
+        """Capacities are agreed ONCE, at the first exchange (every rank is in that step); later steps never re-negotiate — a
+        collective only some ranks enter would hang — so a step whose local count exceeds the agreement raises, and the
+        caller does this BEFORE any collective of the step is entered."""
+        if local > cap:
+            raise RuntimeError(self._OVER_CAPACITY % dict(local=local, table='.'.join(path), cap=cap))
+
+    def _union_buffers(self, info, p, cap):
+        """``info['xchg']``: the union of the ranks' touched rows of one table, and the coalesce workspace that builds it
+        (HotPathModule.check_index_errors reads the union's status word from ``x['ws']``)."""
+        x = info.get('xchg')
+        if x is None or x['cap'] != cap or x['world'] != self.world:
+            from . import _lib
+            dev = p.device
+            ucap = max(1, min(self.world * cap, p.shape[0]))
+            x = dict(cap=cap, world=self.world, ucap=ucap,
+                     urows=torch.empty(ucap, device=dev, dtype=torch.int64),
+                     ucount=torch.zeros(1, device=dev, dtype=torch.int32),
+                     ws=torch.zeros(_lib.load().ps_coalesce_ws_bytes(p.shape[0]), device=dev, dtype=torch.uint8))
+            info['xchg'] = x
+        return x
+
+    def _all_reduce_small(self):
+        m = self.model
+        with _comm('all_reduce(small tensors)'):
+            dist.all_reduce(m._grad_flat[:getattr(m, '_n_allreduce_grad', m._n_dense_grad)], op=dist.ReduceOp.SUM, group=self.group)
+
+    @staticmethod
+    def _install_union(info):
+        x = info['xchg']
+        info['active'] = (x['urows'], x['ucount'], x['ucap'])     # what the optimizer / zero_grad walk this step
+
+
+class SparseGradExchange(_RowExchange):
     """Data-parallel exchange in row-sparse mode (``args.row_sparse_adam``) with NO host synchronisation.
 
     Per step: one all-reduce of the dense head of the flat gradient buffer (small tensors, 0.86 MB at C2), and per
@@ -135,23 +181,20 @@ class SparseGradExchange(object):
     Adam see identical data on every rank without another collective.  xGMI is point-to-point: an all-gather keeps
     all 7 links busy where a ring all-reduce of a table-sized buffer would be bound by one."""
 
+    _OVER_CAPACITY = ("row-sparse exchange: this rank's step addresses up to %(local)d rows of a table but the ranks "
+                      "agreed on messages of %(cap)d rows at the first step; build the exchange after setting "
+                      "args.batch_size / uprev_review_limit to the largest batch any rank will see")
+
     def __init__(self, model, optim=None, group=None):
         _refuse_frozen_words(model)
-        self.model = model
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self._flat = _flat_gather_supported(group) if self.world > 1 else True
+        _RowExchange.__init__(self, model, optim, group)
         self._capacity = {}          # table -> message capacity every rank agreed on (rows)
-        if optim is not None:
-            optim.grad_scale = 1.0 / self.world
 
     def _agree_capacity(self, p, bound):
         """all_gather_into_tensor needs the SAME message size on every rank, but a rank's index count depends on its
         batch (ragged last batch with drop_last=False, history width padded to the batch's own maximum).  The capacity is
-        therefore agreed ONCE per table, the first time the exchange runs (every rank is in that step): MAX over ranks of
-        the largest index count the rank's batch size allows under the model's flags (``model._index_cap_bound``), one
-        host sync.  Later steps never re-negotiate — a collective only some ranks enter would hang — so a step whose
-        local count exceeds the agreement raises before any collective is entered."""
+        therefore agreed ONCE per table, the first time the exchange runs: MAX over ranks of the largest index count the
+        rank's batch size allows under the model's flags (``model._index_cap_bound``), one host sync."""
         t = torch.tensor([int(bound)], dtype=torch.int64, device=p.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         cap = max(1, min(int(t[0]), p.shape[0]))
@@ -159,21 +202,13 @@ class SparseGradExchange(object):
         return cap
 
     def _buffers(self, info, p, cap):
-        x = info.get('xchg')
-        if x is None or x['cap'] != cap or x['world'] != self.world:
-            from . import _lib
-            lib = _lib.load()
+        x = self._union_buffers(info, p, cap)
+        if 'msg_rows' not in x:
             dev, d, W = p.device, p.shape[1], self.world
-            ucap = max(1, min(W * cap, p.shape[0]))
-            x = dict(cap=cap, world=W, ucap=ucap,
-                     msg_rows=torch.empty(cap, device=dev, dtype=torch.int64),
+            x.update(msg_rows=torch.empty(cap, device=dev, dtype=torch.int64),
                      msg_vals=torch.empty(cap, d, device=dev, dtype=torch.float32),
                      all_rows=torch.empty(W, cap, device=dev, dtype=torch.int64),
-                     all_vals=torch.empty(W, cap, d, device=dev, dtype=torch.float32),
-                     urows=torch.empty(ucap, device=dev, dtype=torch.int64),
-                     ucount=torch.zeros(1, device=dev, dtype=torch.int32),
-                     ws=torch.zeros(lib.ps_coalesce_ws_bytes(p.shape[0]), device=dev, dtype=torch.uint8))
-            info['xchg'] = x
+                     all_vals=torch.empty(W, cap, d, device=dev, dtype=torch.float32))
         return x
 
     def __call__(self):
@@ -182,28 +217,24 @@ class SparseGradExchange(object):
         from . import _lib
         lib = _lib.load()
         m = self.model
-        # capacities first (first step only), and the local check, BEFORE any collective of this step is entered
         caps = []
         for path, p, gview in m._sparse_tabs:
             local = int(p._ps_rows['cap'])
             cap = self._capacity.get(id(p))
             if cap is None:
                 cap = self._agree_capacity(p, max(local, m._index_cap_bound(path)))
-            if local > cap:
-                raise RuntimeError("row-sparse exchange: this rank's step addresses up to %d rows of a table but the ranks "
-                                   "agreed on messages of %d rows at the first step; build the exchange after setting "
-                                   "args.batch_size / uprev_review_limit to the largest batch any rank will see" % (local, cap))
+            self._check_capacity(local, cap, path)
             caps.append(cap)
-        with _comm('all_reduce(small tensors)'):
-            dist.all_reduce(m._grad_flat[:getattr(m, '_n_allreduce_grad', m._n_dense_grad)], op=dist.ReduceOp.SUM, group=self.group)
+        self._all_reduce_small()
         for (_, p, gview), cap in zip(m._sparse_tabs, caps):
             info = p._ps_rows
             d = p.shape[1]
             x = self._buffers(info, p, cap)
             st = torch.cuda.current_stream(p.device).cuda_stream
-            # the rank's list holds at most info['cap'] <= cap rows: the message is padded with -1 / zeros up to cap
-            _lib.check(lib.ps_pack_rows(gview.data_ptr(), d, info['rows'].data_ptr(), info['count'].data_ptr(), cap,
-                                        x['msg_rows'].data_ptr(), x['msg_vals'].data_ptr(), st), 'ps_pack_rows')
+            # the rank's list holds info['cap'] <= cap rows: the message is padded with -1 / zeros up to cap
+            _lib.check(lib.ps_pack_rows(gview.data_ptr(), d, p.shape[0], info['rows'].data_ptr(), info['count'].data_ptr(),
+                                        info['cap'], cap, x['msg_rows'].data_ptr(), x['msg_vals'].data_ptr(), st),
+                       'ps_pack_rows')
             with _comm('all_gather(row ids + rows)'):
                 _all_gather_flat(x['all_rows'], x['msg_rows'], self.world, self.group, self._flat)
                 _all_gather_flat(x['all_vals'], x['msg_vals'], self.world, self.group, self._flat)
@@ -214,7 +245,7 @@ class SparseGradExchange(object):
             _lib.check(lib.ps_merge_rows(x['all_rows'].data_ptr(), x['all_vals'].data_ptr(), self.world, cap, d,
                                          gview.data_ptr(), x['urows'].data_ptr(), x['ucount'].data_ptr(), x['ucap'],
                                          st), 'ps_merge_rows')
-            info['active'] = (x['urows'], x['ucount'], x['ucap'])     # what the optimizer / zero_grad walk this step
+            self._install_union(info)
         return None
 
 
@@ -233,7 +264,7 @@ def row_msg_layout(caps, ds):
     return list(io[:n]), list(vo[:n]), int(nbytes)
 
 
-class TablesGradExchange(object):
+class TablesGradExchange(_RowExchange):
     """``SparseGradExchange``'s protocol with every row-sparse table of the model in ONE message (``mode='tables'``).
 
     Table by table the row exchange costs two all-gathers and five launches per table — 8 latency-bound collectives and 20
@@ -247,6 +278,10 @@ class TablesGradExchange(object):
     step whose local capacity exceeds the agreement raises before any collective is entered.  Works over
     ``model._sparse_tabs`` of any row-sparse model (the item models' default stays ``SparseGradExchange``)."""
 
+    _OVER_CAPACITY = ("row exchange: this rank's step addresses up to %(local)d rows of %(table)s but the ranks agreed on "
+                      "messages of %(cap)d rows at the first step; set args.batch_size / uprev_review_limit / "
+                      "iprev_review_limit / max_query_len to the largest batch any rank will see")
+
     def __init__(self, model, optim=None, group=None):
         _refuse_frozen_words(model, tables=True)
         a = getattr(model, 'args', None)
@@ -257,18 +292,12 @@ class TablesGradExchange(object):
         if not getattr(model, '_row_sparse', lambda: False)():
             raise NotImplementedError("mode='tables' exchanges touched rows: this model is not row-sparse "
                                       "(args.row_sparse_adam is off)")
-        self.model = model
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self._flat = _flat_gather_supported(group) if self.world > 1 else True
+        _RowExchange.__init__(self, model, optim, group)
         self._caps = None            # per table of model._sparse_tabs: the message capacity every rank agreed on (rows)
         self._msg = None
-        if optim is not None:
-            optim.grad_scale = 1.0 / self.world
 
     def _agree_capacities(self, bounds, tabs):
-        """ONE MAX all-reduce over the vector of the tables' bounds (one host sync, first exchange only: every rank is in
-        that step).  Later steps never re-negotiate — a collective only some ranks enter would hang."""
+        """ONE MAX all-reduce over the vector of the tables' bounds (one host sync, first exchange only)."""
         t = torch.tensor([int(b) for b in bounds], dtype=torch.int64, device=tabs[0][1].device)
         with _comm('all_reduce(row capacities)'):
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
@@ -284,19 +313,6 @@ class TablesGradExchange(object):
                              all=torch.empty(W, nbytes, device=dev, dtype=torch.uint8))
         return self._msg
 
-    def _table_buffers(self, info, p, cap):
-        x = info.get('xchg')
-        if x is None or x['cap'] != cap or x['world'] != self.world:
-            from . import _lib
-            dev = p.device
-            ucap = max(1, min(self.world * cap, p.shape[0]))
-            x = dict(cap=cap, world=self.world, ucap=ucap,
-                     urows=torch.empty(ucap, device=dev, dtype=torch.int64),
-                     ucount=torch.zeros(1, device=dev, dtype=torch.int32),
-                     ws=torch.zeros(_lib.load().ps_coalesce_ws_bytes(p.shape[0]), device=dev, dtype=torch.uint8))
-            info['xchg'] = x         # (HotPathModule.check_index_errors reads the union's status word from x['ws'])
-        return x
-
     def message_bytes(self):
         """Bytes of one rank's message (None before the first exchange)."""
         return None if self._msg is None else self._msg['bytes']
@@ -310,37 +326,30 @@ class TablesGradExchange(object):
         tabs = m._sparse_tabs
         if not tabs:
             raise RuntimeError("mode='tables': the model has no row-sparse table to exchange")
-        # capacities first (first step only), and the local check, BEFORE any collective of this step is entered
         local = [int(p._ps_rows['cap']) for _, p, _ in tabs]
         if self._caps is None:
             self._agree_capacities([max(c, m._index_cap_bound(path)) for c, (path, _, _) in zip(local, tabs)], tabs)
         for c, cap, (path, _, _) in zip(local, self._caps, tabs):
-            if c > cap:
-                raise RuntimeError("row exchange: this rank's step addresses up to %d rows of %s but the ranks agreed on "
-                                   "messages of %d rows at the first step; set args.batch_size / uprev_review_limit / "
-                                   "iprev_review_limit / max_query_len to the largest batch any rank will see"
-                                   % (c, '.'.join(path), cap))
+            self._check_capacity(c, cap, path)
         msg = self._buffers(tabs)
         arr = (_lib.PsRowMsgTable * len(tabs))()
         for t, (_, p, gview), c, cap in zip(arr, tabs, local, self._caps):
             info = p._ps_rows
-            x = self._table_buffers(info, p, cap)
+            x = self._union_buffers(info, p, cap)
             t.cap, t.d, t.n_rows, t.grad_dev = cap, p.shape[1], p.shape[0], gview.data_ptr()
             t.rows_dev, t.count_dev, t.list_cap = info['rows'].data_ptr(), info['count'].data_ptr(), c
             t.ws_dev, t.union_rows_dev, t.union_cap = x['ws'].data_ptr(), x['urows'].data_ptr(), x['ucap']
             t.union_count_dev = x['ucount'].data_ptr()
         st = torch.cuda.current_stream(tabs[0][1].device).cuda_stream
         n, nbytes = len(tabs), msg['bytes']
-        with _comm('all_reduce(small tensors)'):
-            dist.all_reduce(m._grad_flat[:getattr(m, '_n_allreduce_grad', m._n_dense_grad)], op=dist.ReduceOp.SUM, group=self.group)
+        self._all_reduce_small()
         _lib.check(lib.ps_pack_tables(arr, n, msg['mine'].data_ptr(), nbytes, st), 'ps_pack_tables')
         with _comm('all_gather(row message)'):
             _all_gather_flat(msg['all'], msg['mine'], self.world, self.group, self._flat)
         _lib.check(lib.ps_union_tables(arr, n, msg['all'].data_ptr(), nbytes, self.world, st), 'ps_union_tables')
         _lib.check(lib.ps_merge_tables(arr, n, msg['all'].data_ptr(), nbytes, self.world, st), 'ps_merge_tables')
         for _, p, _ in tabs:
-            x = p._ps_rows['xchg']
-            p._ps_rows['active'] = (x['urows'], x['ucount'], x['ucap'])     # what the optimizer / zero_grad walk this step
+            self._install_union(p._ps_rows)
         return None
 
 

@@ -319,7 +319,7 @@ class HotPathModule(nn.Module):
 
     def _coalesce_touched(self, plan):
         """The sorted unique non-pad row ids of the step's index lists, per row-sparse table (``p._ps_rows``): one
-        ``ps_coalesce_tables`` call when several tables have lists, ``ps_coalesce_rows`` for a single one."""
+        ``ps_coalesce_tables`` call for every ``_lib.PS_MAX_COALESCE_TABLES`` tables that have lists."""
         lib = _lib.load()
         dev, st = self._dev(), self._stream()
         work = []
@@ -340,23 +340,16 @@ class HotPathModule(nn.Module):
                 info['count'].zero_()
                 continue
             work.append((p, info, lists, pad))
-        if len(work) > 1 and len(work) <= _lib.PS_MAX_COALESCE_TABLES:
-            tabs = (_lib.PsCoalesceTable * len(work))()
-            for t, (p, info, lists, pad) in zip(tabs, work):
+        for k in range(0, len(work), _lib.PS_MAX_COALESCE_TABLES):
+            chunk = work[k:k + _lib.PS_MAX_COALESCE_TABLES]
+            tabs = (_lib.PsCoalesceTable * len(chunk))()
+            for t, (p, info, lists, pad) in zip(tabs, chunk):
                 for i, x in enumerate(lists):
                     t.lists[i].idx, t.lists[i].n = x.data_ptr(), x.numel()
                 t.n_lists, t.n_rows, t.pad_row = len(lists), p.shape[0], pad
                 t.ws_dev, t.rows_out_dev, t.cap = info['ws'].data_ptr(), info['rows'].data_ptr(), info['rows'].numel()
                 t.count_out_dev = info['count'].data_ptr()
-            _lib.check(lib.ps_coalesce_tables(tabs, len(work), st), 'ps_coalesce_tables')
-        else:
-            for p, info, lists, pad in work:
-                arr = (_lib.PsIdxList * len(lists))()
-                for i, t in enumerate(lists):
-                    arr[i].idx, arr[i].n = t.data_ptr(), t.numel()
-                _lib.check(lib.ps_coalesce_rows(arr, len(lists), p.shape[0], pad, info['ws'].data_ptr(),
-                                                info['rows'].data_ptr(), info['rows'].numel(),
-                                                info['count'].data_ptr(), st), 'ps_coalesce_rows')
+            _lib.check(lib.ps_coalesce_tables(tabs, len(chunk), st), 'ps_coalesce_tables')
         for _, info, _, _ in work:
             info['dirty'] = True
 

@@ -50,6 +50,57 @@ def test_coalesce_rows_is_sorted_unique(n_rows, sizes):
     assert np.array_equal(got2, want)
 
 
+def _coalesce_raw(lists, n_rows, pad, ws=None):
+    """ps_coalesce_rows with everything it wrote kept: (the whole rows_out buffer, pre-filled with -7; count; workspace)."""
+    from prodsearch_amd import _lib
+    lib = _lib.load()
+    ts = [torch.as_tensor(x, dtype=torch.int64, device='cuda') for x in lists]
+    cap = max(1, min(sum(t.numel() for t in ts), n_rows))
+    if ws is None:
+        ws = torch.zeros(lib.ps_coalesce_ws_bytes(n_rows), dtype=torch.uint8, device='cuda')
+    rows = torch.full((cap,), -7, dtype=torch.int64, device='cuda')
+    count = torch.full((1,), -7, dtype=torch.int32, device='cuda')
+    arr = (_lib.PsIdxList * len(ts))()
+    for i, t in enumerate(ts):
+        arr[i].idx, arr[i].n = t.data_ptr(), t.numel()         # (an empty list comes with a null pointer)
+    _lib.check(lib.ps_coalesce_rows(arr, len(ts), n_rows, pad, ws.data_ptr(), rows.data_ptr(), cap,
+                                    count.data_ptr(), torch.cuda.current_stream().cuda_stream), 'ps_coalesce_rows')
+    torch.cuda.synchronize()
+    return rows.cpu().numpy(), int(count[0]), ws
+
+
+# the edges of the block and word grid: one word, a full word, one bit into the second word, a full block of 256 words, one
+# bit into the second block.  pad 'last' is the models' convention (the table's last row), -1 the exchanges'
+@pytest.mark.parametrize('n_rows,pad', [(1, -1), (64, -1), (64, 'last'), (65, -1), (65, 'last'), (16384, -1), (16384, 'last'),
+                                        (16385, -1), (16385, 'last')])
+def test_coalesce_rows_at_the_edges_of_the_block_and_word_grid(n_rows, pad):
+    pad = n_rows - 1 if pad == 'last' else pad
+    rng = np.random.default_rng(7 * n_rows + pad)
+    s = 200
+    x = rng.integers(0, n_rows, size=s)
+    x[rng.random(s) < 0.2] = pad                            # about a fifth of the entries are pads
+    x[:2] = [0, n_rows - 1]                                 # first and last row (the last one IS the pad under 'last')
+    if pad == n_rows - 1:
+        x[2] = n_rows - 2                                   # ... then the last real row
+    lists = [x, np.zeros(0, np.int64)]                      # two lists, one of them empty
+    want = np.unique(x)
+    want = want[want != pad]
+    n_bitmap = 8 * ((n_rows + 63) // 64)
+    rows, count, ws = _coalesce_raw(lists, n_rows, pad)
+    assert count == len(want) and np.array_equal(rows[:count], want)            # bit-exact index work
+    assert bool((rows[count:] == -7).all())                                     # nothing written past the count
+    assert int(ws[:n_bitmap].to(torch.int32).sum()) == 0                        # bitmap left clean
+    rows2, count2, _ = _coalesce_raw(lists[::-1], n_rows, pad, ws)              # the same workspace again: the same answer
+    assert count2 == count and np.array_equal(rows2, rows)
+    # lists that hold pads only: count 0, output untouched, bitmap still clean
+    rows3, count3, _ = _coalesce_raw([np.full(37, pad), np.zeros(0, np.int64)], n_rows, pad, ws)
+    assert count3 == 0 and bool((rows3 == -7).all())
+    assert int(ws[:n_bitmap].to(torch.int32).sum()) == 0
+    addr = __import__('prodsearch_amd._lib', fromlist=['x']).load().ps_coalesce_bad_flag(ws.data_ptr(), n_rows)
+    off = addr - ws.data_ptr()
+    assert int(ws[off:off + 4].view(torch.int32)[0]) == 0
+
+
 def test_coalesce_rejects_out_of_range_rows_without_fault():
     got, ws = _coalesce([np.array([3, 5, 10_000_000, -2, 5])], 100, 99)
     assert list(got) == [3, 5]
@@ -202,7 +253,7 @@ def test_pack_and_merge_rows_sum_the_ranks_in_rank_order(world, d):
         rows_dev = torch.full((cap,), 12345, dtype=torch.int64, device='cuda')       # garbage past count must not leak
         rows_dev[:n] = torch.from_numpy(rows).cuda()
         cnt = torch.tensor([n], dtype=torch.int32, device='cuda')
-        _lib.check(lib.ps_pack_rows(grad.data_ptr(), d, rows_dev.data_ptr(), cnt.data_ptr(), cap,
+        _lib.check(lib.ps_pack_rows(grad.data_ptr(), d, n_rows, rows_dev.data_ptr(), cnt.data_ptr(), cap, cap,
                                     all_rows[r].data_ptr(), all_vals[r].data_ptr(), st), 'ps_pack_rows')
         ref.index_add_(0, torch.from_numpy(rows), vals)                              # (0 + r0) + r1 + ...: rank order
         union |= set(rows.tolist())
@@ -231,6 +282,71 @@ def test_pack_and_merge_rows_sum_the_ranks_in_rank_order(world, d):
     assert int(ws[off:off + 4].view(torch.int32)[0]) == 0
 
 
+@pytest.mark.parametrize('world,d', [(8, 4), (32, 8), (3, 132)])
+def test_merge_rows_narrower_than_the_world(world, d):
+    """Rows with fewer float4s than the world has ranks (d < 4 * world: every rank's position must still reach the lanes
+    that add), and d = 132: a second trip of the 32-lane loop that only one lane takes."""
+    from prodsearch_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    n_rows, cap = 300, 8
+    rng = np.random.default_rng(100 * world + d)
+    shared = np.array([0, 64, n_rows - 1])                                          # sent by every rank
+    pool = rng.permutation(np.setdiff1d(np.arange(n_rows), shared))
+    all_rows = torch.full((world, cap), -1, dtype=torch.int64)
+    all_vals = torch.full((world, cap, d), float('nan'))                            # slots past a rank's count are never read
+    ref = torch.zeros(n_rows, d)
+    union = set()
+    for r in range(world):
+        own, pool = pool[:r % 6], pool[r % 6:]                                       # sent by this rank only (0 .. 5 ids)
+        rows = np.sort(np.concatenate([shared, own]))
+        vals = torch.randn(len(rows), d)
+        all_rows[r, :len(rows)] = torch.from_numpy(rows)
+        all_vals[r, :len(rows)] = vals
+        ref.index_add_(0, torch.from_numpy(rows), vals)                              # (0 + r0) + r1 + ...: rank order
+        union |= set(rows.tolist())
+    want_union = np.array(sorted(union))
+    ucap = min(world * cap, n_rows)
+    urows = torch.full((ucap,), 12345, dtype=torch.int64)                            # garbage past the count
+    urows[:len(want_union)] = torch.from_numpy(want_union)
+    all_rows, all_vals, urows = all_rows.cuda(), all_vals.cuda(), urows.cuda()
+    ucount = torch.tensor([len(want_union)], dtype=torch.int32, device='cuda')
+    grad = torch.full((n_rows, d), 7.0, device='cuda')                               # merged rows are OVERWRITTEN, others untouched
+    _lib.check(lib.ps_merge_rows(all_rows.data_ptr(), all_vals.data_ptr(), world, cap, d, grad.data_ptr(),
+                                 urows.data_ptr(), ucount.data_ptr(), ucap, st), 'ps_merge_rows')
+    torch.cuda.synchronize()
+    got = grad.cpu()
+    assert torch.equal(got[torch.from_numpy(want_union)], ref[torch.from_numpy(want_union)])      # bitwise
+    mask = torch.ones(n_rows, dtype=torch.bool)
+    mask[torch.from_numpy(want_union)] = False
+    assert bool(mask.any()) and bool((got[mask] == 7.0).all())
+
+
+@pytest.mark.parametrize('d', [4, 132])
+@pytest.mark.parametrize('count', [0, 2, 3])
+def test_pack_rows_with_a_list_shorter_than_the_message(count, d):
+    """The touched list's allocation (list_cap = 3) is shorter than the agreed message (cap = 7, odd): slots past the count are
+    -1 / zeros, nothing behind the list is read, and nothing behind the message's cap entries is written."""
+    from prodsearch_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    n_rows, cap, list_cap, huge, canary = 50, 7, 3, 1 << 40, -4242
+    grad = torch.randn(n_rows, d, device='cuda')
+    rows = torch.full((8,), huge, dtype=torch.int64)                                # past the count: an id that must not leak
+    rows[:count] = torch.tensor([5, 17, n_rows - 1])[:count]
+    rows = rows.cuda()
+    cnt = torch.tensor([count], dtype=torch.int32, device='cuda')
+    msg_rows = torch.full((cap + 1,), canary, dtype=torch.int64, device='cuda')
+    msg_vals = torch.full((cap + 1, d), float(canary), device='cuda')
+    _lib.check(lib.ps_pack_rows(grad.data_ptr(), d, n_rows, rows.data_ptr(), cnt.data_ptr(), list_cap, cap,
+                                msg_rows.data_ptr(), msg_vals.data_ptr(), st), 'ps_pack_rows')
+    torch.cuda.synchronize()
+    live = rows[:count]
+    assert msg_rows[:cap].tolist() == live.tolist() + [-1] * (cap - count)
+    assert torch.equal(msg_vals[:count], grad[live]) and bool((msg_vals[count:cap] == 0).all())
+    assert int(msg_rows[cap]) == canary and bool((msg_vals[cap] == float(canary)).all())
+
+
 def test_index_errors_are_reported_when_asked():
     import copy
     from prodsearch_amd import ItemTransformerRanker
@@ -249,7 +365,7 @@ def test_index_errors_are_reported_when_asked():
     info = m.product_emb.weight._ps_rows
     lib = __import__('prodsearch_amd._lib', fromlist=['x']).load()
     off = lib.ps_coalesce_bad_flag(info['ws'].data_ptr(), m.product_emb.weight.shape[0]) - info['ws'].data_ptr()
-    info['ws'][off:off + 4].view(torch.int32)[0] = 1         # what co_mark_kernel sets for an out-of-range index
+    info['ws'][off:off + 4].view(torch.int32)[0] = 1         # what co_mark_tabs_kernel sets for an out-of-range index
     with pytest.raises(RuntimeError, match='outside'):
         m.check_index_errors()
     m.check_index_errors()                                   # the flag is cleared once reported
