@@ -212,6 +212,22 @@ int ps_gemm_x3_config(int mode, int force_shape);
  * (ps_gemm_x3_config(1, 4), M >= 4096, N / K multiples of 32), otherwise as ps_gemm_f32 would.  What the d >= 256 step's forward / dX products do. */
 int ps_gemm_f32_weight(const float* A, int lda, const float* W, int tb, float* C, int ldc, int M, int N, int K,
                        const float* bias, float alpha, ps_stream_t stream);
+/* Which kernel a group of products takes (no reference counterpart; csrc/gemm.hip, gemm_plan — the function every launch goes
+ * through; DESIGN.md, "which kernel a product takes").  A member is described by its shape and layouts, full (0: the plain
+ * epilogue, 1: an activation, 2: dropout — both need the full one), listed (a row list), accumulate (0 store, 1 +=, 2 atomic),
+ * split_stride (> 0: per-split outputs), no_deep and kseg (reduction rows per B segment; 0: one segment).  flat / prefer_x3d: the
+ * group's fields of the same name; planes: weight planes are registered for every member (ps_gemm_f32_weight's scope).  The plan:
+ * family 0 fp32 / 1 bf16x3 / 2 bf16x3 direct-to-LDS / 3 bf16x3 pre-split weights; the instantiation (ta, tb, full, idx); bk / pf
+ * (slab depth, slabs in flight); the tile; flat (1-D grid) and redirected (asked for on the 3-D grid, sent to the flat one); the
+ * grid; dynamic LDS bytes; the XCD placement masks.  Host only: no HIP call, works without a device — the group is filled with
+ * dummy addresses that are never dereferenced.  A group no launch would accept is refused with the launch's own message. */
+typedef struct PsGemmMember {
+  int32_t M, N, K, ksplit, ta, tb, full, listed, accumulate, split_stride, no_deep, kseg;
+} PsGemmMember;
+typedef struct PsGemmPlan {
+  int32_t family, ta, tb, full, idx, bk, pf, tile_m, tile_n, flat, redirected, grid_x, grid_y, grid_z, lds_bytes, flat_xcd, split_xcd;
+} PsGemmPlan;
+int ps_gemm_plan(int32_t n, const PsGemmMember* members, int32_t flat, int32_t prefer_x3d, int32_t planes, PsGemmPlan* out);
 
 /* Workspace the caller allocates once per shape (bytes) and its layout. */
 int ps_tem_workspace_layout(const PsTemDesc* desc, PsTemWsLayout* out);

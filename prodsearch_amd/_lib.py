@@ -58,6 +58,16 @@ class PsEncPath(C.Structure):
                                          'wg3_last', 'wgrad_early', 'q_folded', 'listed', 'presum', 'dx_fused', 'wf_key_split')]
 
 
+class PsGemmMember(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('M', 'N', 'K', 'ksplit', 'ta', 'tb', 'full', 'listed', 'accumulate', 'split_stride',
+                                         'no_deep', 'kseg')]
+
+
+class PsGemmPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('family', 'ta', 'tb', 'full', 'idx', 'bk', 'pf', 'tile_m', 'tile_n', 'flat', 'redirected',
+                                         'grid_x', 'grid_y', 'grid_z', 'lds_bytes', 'flat_xcd', 'split_xcd')]
+
+
 class PsAdamHyper(C.Structure):
     _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
                 ('weight_decay', C.c_float), ('max_grad_norm', C.c_float), ('noam', C.c_int32),
@@ -182,6 +192,7 @@ SYMBOLS = {
     'ps_gemm_x3_config': (C.c_int, [C.c_int, C.c_int]),
     'ps_gemm_f32_weight': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_float, C.c_void_p]),
+    'ps_gemm_plan': (C.c_int, [C.c_int32, C.POINTER(PsGemmMember), C.c_int32, C.c_int32, C.c_int32, C.POINTER(PsGemmPlan)]),
     'ps_tem_workspace_layout': (C.c_int, [C.POINTER(PsTemDesc), C.POINTER(PsTemWsLayout)]),
     'ps_tem_forward': (C.c_int, [C.POINTER(PsTemDesc), C.POINTER(PsTemTensors), C.POINTER(PsTemBatch),
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

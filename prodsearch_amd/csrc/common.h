@@ -373,7 +373,7 @@ struct GemmProblem {
                                         // stores its own partial matrix, a second launch adds them up in split order)
   int no_deep;                          // never pick the 128-deep-slab form (133 KB of LDS per workgroup): for small products that
                                         // run BESIDE other launches, where that footprint starves them of CUs
-  // filled by the launcher (gemm.hip, WPlaneScope): the B segments as pre-split bf16 plane matrices [3][N][kseg] (hi / mid / lo,
+  // filled by the launcher (gemm.hip, from its plan; WPlaneScope): the B segments as pre-split bf16 plane matrices [3][N][kseg] (hi / mid / lo,
   // reduction index contiguous whatever tb says), or null — gemm_x3w_kernel reads B from them
   const uint16_t* bpl[3];
 };

@@ -40,7 +40,7 @@ static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTem
   if (tem && rows_list_ok(D)) { e.vrows = reinterpret_cast<int32_t*>(ws + w.vrows); e.vcount = reinterpret_cast<int32_t*>(ws + w.vcount); }
   const float* wp_w[PS_WPLANES_MAX]; int wp_r[PS_WPLANES_MAX], wp_c[PS_WPLANES_MAX];
   const int wp_n = wplane_list(D, P, w, wp_w, wp_r, wp_c);
-  WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the big linears multiply against pre-split weight planes (gemm.hip)
+  WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the big linears multiply against pre-split weight planes (gemm_kernels.hip)
   if (samp) {
     e.samp_prob = samp->prob; e.samp_alias = samp->alias; e.samp_items = samp->items; e.samp_words = samp->words;
     e.samp_nitem = D.B * D.K; e.samp_nword = D.B * D.W * D.K; e.samp_step = (uint32_t)D.step;
@@ -260,7 +260,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
 
   const float* wp_w[PS_WPLANES_MAX]; int wp_r[PS_WPLANES_MAX], wp_c[PS_WPLANES_MAX];
   const int wp_n = wplane_list(D, P, w, wp_w, wp_r, wp_c);
-  WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the dX products read the TRANSPOSED weight planes (gemm.hip)
+  WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the dX products read the TRANSPOSED weight planes (gemm_kernels.hip)
   ColFoldList fold;
   fold.n = 0;
   const float* dqe = ws + w.denc;   // grad wrt query_emb rows (QEM: enc IS query_emb)
