@@ -143,6 +143,23 @@ int ps_set_fuse_bwd_min(int rows);
  * the previous value.  ps_item_scatter_fused_taken: 1 when the last backward of this process took it. */
 int ps_set_item_scatter_fused(int on);
 int ps_item_scatter_fused_taken(void);
+/* Tuning knob (no reference counterpart): the one-layer d = 128 forward with replicas (attention form kvq) embeds its
+ * sequences inside the projection + attention launch — one launch instead of two (default 1, env PS_FRONT_FUSED; 0 = the embed
+ * launch in front, as PS_KVQ_FUSED=0 implies).  FS query encoder, positional rows, at most 16 query words; anything else keeps
+ * the two launches.  Returns the previous value.  ps_front_fused_taken: 1 when the last forward of this process took it (the
+ * attention form stays 4 with rowlist = 1 in ps_tem_plan and ps_enc_path_taken; PsEncPath has no field for it). */
+int ps_set_front_fused(int on);
+int ps_front_fused_taken(void);
+/* Unit-test hook of that form: ps_tem_forward_sampled twice from the same inputs — the two launches into ws_a, the one launch
+ * into ws_b (neg_* / loss3_*: each run's draws and loss) — and the largest absolute difference of what the front end and its
+ * riders leave, per region (a value that differs only as a NaN counts as infinity), in this order: x, qmean_d, query_emb,
+ * kp, vp (valid positions only), qp, attn, amask, ctx, word_scores, word_terms, neg items, neg words, vrows (the listed part),
+ * vcount.  taken[0] / taken[1]: ps_front_fused_taken() after each run.  Synchronises the stream. */
+#define PS_FRONT_TEST_REGIONS 15
+int ps_front_fused_test(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch, const float* alias_prob,
+                        const int32_t* alias_idx, float* ws_a, float* ws_b, int64_t* neg_item_a, int64_t* neg_word_a,
+                        int64_t* neg_item_b, int64_t* neg_word_b, float* loss3_a, float* loss3_b, double* diff,
+                        int32_t* taken, ps_stream_t stream);
 /* Which kernels an item-transformer step launches (no reference counterpart; csrc/encoder.h, EncPlan): one attention form per
  * layer and the forms of the steps around it.  Forward: rowlist (K / V products over the valid-row list), fwd_fuse_last (the
  * last layer's Wo + LN + FFN + final LN as one kernel), fold_score (... with item scoring and the loss in its epilogue).

@@ -182,6 +182,11 @@ SYMBOLS = {
     'ps_set_fuse_bwd_min': (C.c_int, [C.c_int]),
     'ps_set_item_scatter_fused': (C.c_int, [C.c_int]),
     'ps_item_scatter_fused_taken': (C.c_int, []),
+    'ps_set_front_fused': (C.c_int, [C.c_int]),
+    'ps_front_fused_taken': (C.c_int, []),
+    'ps_front_fused_test': (C.c_int, [C.POINTER(PsTemDesc), C.POINTER(PsTemTensors), C.POINTER(PsTemBatch), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
     'ps_tem_plan': (C.c_int, [C.POINTER(PsTemDesc), C.POINTER(PsTemTensors), C.c_int32, C.POINTER(PsEncPath)]),
     'ps_enc_path_taken': (C.c_int, [C.c_int32, C.POINTER(PsEncPath)]),
     'ps_set_side_mode': (C.c_int, [C.c_int]),

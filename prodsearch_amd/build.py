@@ -14,7 +14,7 @@ LIB = os.path.join(LIBDIR, 'libprodsearch_hip.so')
 DIAG_LIB = os.path.join(LIBDIR, 'libprodsearch_hip_diag.so')      # -DPS_DIAG: tuning knobs, stamps, timing-only variants (tools/)
 SOURCES = ['gemm.hip', 'gemm_kernels.hip', 'rowwise.hip', 'attn_sq1.hip', 'mlp_fused.hip', 'optim.hip', 'optim_rows.hip', 'rank.hip', 'runtime.hip', 'side_stream.hip', 'wgrad.hip',
            'encoder.hip', 'tem.hip', 'rtm.hip', 'rtm_embed.hip', 'rtm_score.hip', 'rtm_index.hip', 'rtm_embed_bwd.hip', 'rtm_rank.hip', 'attn_emb.hip']
-HEADERS = ['common.h', 'gemm.h', 'rowwise.h', 'encoder.h', 'side_stream.h', 'wgrad.h', 'rtm.h', 'rank.h', 'optim_core.h', 'graph.h', 'x3frag.h',
+HEADERS = ['common.h', 'gemm.h', 'rowwise.h', 'encoder.h', 'side_stream.h', 'wgrad.h', 'rtm.h', 'rank.h', 'optim_core.h', 'graph.h', 'x3frag.h', 'embed_riders.h',
            os.path.join('..', '..', 'include', 'prodsearch_hip.h'), os.path.join('..', '..', 'include', 'prodsearch_rtm_cand.h'),
            os.path.join('..', '..', 'include', 'prodsearch_rtm_seq.h')]
 

@@ -11,6 +11,7 @@
 #include "rowwise.h"
 #include "side_stream.h"
 #include "x3frag.h"
+#include "embed_riders.h"
 #include <stdlib.h>
 
 #define SQ1_LDS_MAX (128 * 1024)   // dynamic LDS these kernels may request (160 KB per CU on gfx950)
@@ -748,17 +749,28 @@ struct KvqLds {
 #else
 #define KVQ_STAMP(slot) do { } while (0)
 #endif
-template <int MAXK>
-__global__ __launch_bounds__(512, 2) void kvq_attn_fwd_kernel(const KvqArgs g) {      // <= 128 registers: two workgroups per CU, every sequence resident
+struct NoFront {};                    // kvq_sequence_wg<.., false>: no embed arguments
+// valid key positions from the history id a lane already holds (lane s: id of position s, s >= 1): w1_valid without its load
+__device__ inline unsigned long long w1_valid_ids(int S, int64_t P, int lane, int64_t uil, int* sp) {
+  const bool v = lane < S && (lane == 0 || uil != P);
+  const unsigned long long vm = __ballot(v);
+  if (v) sp[__popcll(vm & ((1ull << lane) - 1ull))] = lane;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return vm;
+}
+// One sequence's workgroup (512 threads).  FRONT = false: the sequence's rows of x were written by the embed launch in front and
+// the K / V fragments re-split by its riders (kvq_attn_fwd_kernel).  FRONT = true (front_attn_fwd_kernel): the workgroup first
+// does what the sequence's workgroup of embed_fwd_kernel does (rowwise.hip) — the same expressions in the same order, so x,
+// qmean_d and query_emb are bitwise what that launch stores — puts the rows straight into the LDS planes, and takes its A
+// operand from the fp32 linear_keys / linear_values rows: a fragment chunk of WSplit::fwd_kv is the split of 8 CONTIGUOUS floats
+// of one weight row (wsplit_chunk, which == 4), so two 16-byte loads and split8 give the planes' bits without the planes.
+template <int MAXK, bool FRONT, class EA>
+__device__ __forceinline__ void kvq_sequence_wg(const KvqArgs& g, const EA e, KvqLds& L) {
   constexpr int DH = 16, LPR = DH, KPS = 64 / LPR, HC = 4 * DH, LPH = DH / 4, D = 128;
-  extern __shared__ float kvq_lds_raw[];
-  KvqLds& L = *reinterpret_cast<KvqLds*>(kvq_lds_raw);
   const AttnArgs& a = g.at;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h = lane >> 5;
-  if ((int)blockIdx.x >= a.n_in) {     // the backward-only weight streams are re-split here, under the sequences' workgroups (KvqArgs::split)
-    wsplit_chunk(g.split, 1, ((int)blockIdx.x - a.n_in) * 512 + tid);
-    return;
-  }
   const int b = blockIdx.x, S = a.S, HF = a.H;
 #if PS_DIAG_ON
   unsigned long long kvq_st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -766,35 +778,142 @@ __global__ __launch_bounds__(512, 2) void kvq_attn_fwd_kernel(const KvqArgs g) {
   KVQ_STAMP(0);
   DropSpec drop = a.drop;                                              // (the step word lives in device memory: read it with the rest)
   drop.step = drop_step(a.drop); drop.step_ptr = nullptr;
-  // ---- everything with a global round trip, requested now
-  // (1) the wave's weight fragments: feature block nb = wave & 3 of K (wave < 4) or V
-  const uint16_t* stream = g.kv_stream + (size_t)(wave * 8) * 1536;
-  uint4 wf[4][3];                                                      // a ring of four: steps 4..7 are requested as 0..3 retire
-#pragma unroll
-  for (int t = 0; t < 4; ++t) load_frag(wf[t], stream, t, lane);
-  // (2) x rows -> planes: thread = (position, one 8-element chunk); positions past S are zero rows
-  {
-    const int row = tid >> 4, kc = tid & 15;
-    const float* src = g.x + ((size_t)b * S + (row < S ? row : 0)) * D + 8 * kc;
-    const float4 v0 = f4_ld(src), v1 = f4_ld(src + 4);
-    const bool on = row < S;
-    const float v[8] = {on ? v0.x : 0.f, on ? v0.y : 0.f, on ? v0.z : 0.f, on ? v0.w : 0.f,
-                        on ? v1.x : 0.f, on ? v1.y : 0.f, on ? v1.z : 0.f, on ? v1.w : 0.f};
-    put8(L.Xa, row, 8 * kc, v);
-  }
-  // (3) Q: lane group gq (32 lanes) owns outputs gq + 16 u; lane cq holds 4 elements of the query row and of each weight row
-  const int gq = tid >> 5, cq = tid & 31;
-  const float4 x0 = f4_ld(g.x + (size_t)b * S * D + 4 * cq);
+  const int gq = tid >> 5, cq = tid & 31;                              // 16 lane groups of 32: Q outputs gq + 16 u, 4 columns per lane
+  const int nb = wave & 3, f0 = 32 * nb + 16 * h;
+  uint4 wf[4][3];                                                      // FRONT = false: a ring of four fragment steps (4..7 are requested as 0..3 retire)
+  float4 wraw[4][2];                                                   // FRONT = true: the same ring as raw fp32 chunks
+  const uint16_t* stream = nullptr;
+  const float* wrow = nullptr;
+  float4 x0;
   float4 wq[8];
   float bqv[8];
+  unsigned long long vm;
+  // ---- everything with a global round trip, requested now
+  if constexpr (!FRONT) {
+    // (1) the wave's weight fragments: feature block nb = wave & 3 of K (wave < 4) or V
+    stream = g.kv_stream + (size_t)(wave * 8) * 1536;
 #pragma unroll
-  for (int u = 0; u < 8; ++u) { wq[u] = f4_ld(g.wq + (size_t)(gq + 16 * u) * D + 4 * cq); bqv[u] = g.bq[gq + 16 * u]; }
-  // (4) the sequence's valid positions (every wave keeps its own copy of the list)
-  const unsigned long long vm = w1_valid(a, b, lane, L.sp[wave]);
+    for (int t = 0; t < 4; ++t) load_frag(wf[t], stream, t, lane);
+    // (2) x rows -> planes: thread = (position, one 8-element chunk); positions past S are zero rows
+    {
+      const int row = tid >> 4, kc = tid & 15;
+      const float* src = g.x + ((size_t)b * S + (row < S ? row : 0)) * D + 8 * kc;
+      const float4 v0 = f4_ld(src), v1 = f4_ld(src + 4);
+      const bool on = row < S;
+      const float v[8] = {on ? v0.x : 0.f, on ? v0.y : 0.f, on ? v0.z : 0.f, on ? v0.w : 0.f,
+                          on ? v1.x : 0.f, on ? v1.y : 0.f, on ? v1.z : 0.f, on ? v1.w : 0.f};
+      put8(L.Xa, row, 8 * kc, v);
+    }
+    // (3) Q: lane group gq (32 lanes) owns outputs gq + 16 u; lane cq holds 4 elements of the query row and of each weight row
+    x0 = f4_ld(g.x + (size_t)b * S * D + 4 * cq);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { wq[u] = f4_ld(g.wq + (size_t)(gq + 16 * u) * D + 4 * cq); bqv[u] = g.bq[gq + 16 * u]; }
+    // (4) the sequence's valid positions (every wave keeps its own copy of the list)
+    vm = w1_valid(a, b, lane, L.sp[wave]);
+  } else {
+    // LDS the K / V tiles do not use yet: the 16 lane groups' query-word rows, the FS dropout multipliers, the FS projection
+    float* red = &L.Ks[0][0];                                          // [16][128]
+    float* dms = red + 16 * D;                                         // [128]
+    float* out_s = dms + D;                                            // [128]
+    const int Q = e.Q;
+    const int64_t wpad = e.V - 1;
+    DropSpec dfs = e.drop_fs;
+    dfs.step = drop.step; dfs.step_ptr = nullptr;                      // (one step word for every site of the step)
+    const int row = tid >> 4, kc = tid & 15;                           // plane fill: thread = (position, one 8-element chunk)
+    // rows 1 .. S-1 are the history; the threads of row 0 (written below, by the FS projection) and of the rows past S repeat
+    // a neighbour's row of x — the same values to the same place — and put zeros into the planes: no load or store under a test
+    const int rc = row < 1 ? 1 : (row < S ? row : S - 1);
+    // (0) the ids: the Q query words (lane cq of every group holds word cq), this thread's history id, this lane's position
+    const int64_t qid_l = e.qw[(size_t)b * Q + (cq < Q ? cq : Q - 1)];
+    const int64_t hid = e.ui[(size_t)b * e.L + rc - 1];
+    const int64_t uil = e.ui[(size_t)b * e.L + (lane < 1 ? 0 : (lane < S ? lane - 1 : S - 2))];
+    // (1) the wave's K / V weight rows: row 32 nb + phi(l31) of linear_keys (wave < 4) / linear_values, k = 16 t + 8 h + e
+    const int phi = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+    // (requested behind the FS projection, where the f_W rows retire, as the linear_query rows are behind the gather: the
+    //  prologue does not have the registers to hold all three at once.  They fly across the barriers in between, which are
+    //  raw s_barriers behind an LDS wait for that reason — `__syncthreads` would drain them)
+    wrow = (wave < 4 ? g.wkv[0] : g.wkv[1]) + (size_t)(32 * nb + phi) * D + 8 * h;
+    // (2) the f_W rows this lane group will multiply (outputs gq + 16 u), the linear_query rows, biases, pe rows
+    float4 fsw[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) fsw[u] = f4_ld(e.fs_w + (size_t)(gq + 16 * u) * D + 4 * cq);
+    const float4 pr0 = f4_ld(e.pe + (size_t)rc * D + 8 * kc), pr1 = f4_ld(e.pe + (size_t)rc * D + 8 * kc + 4);
+    // (3) behind the ids: group gq's query-word row, this thread's chunk of its history row (clamped, masked by value)
+    const int64_t qid = __shfl(qid_l, (lane & 32) + (gq & 15), 64);
+    const bool qok = gq < Q && qid != wpad && qid >= 0 && qid < e.V;
+    float4 wr = f4_ld(e.word_emb + (size_t)(qok ? qid : 0) * D + 4 * cq);
+    const bool hok = hid != e.P && hid >= 0 && hid < e.P;
+    const float* hsrc = e.hist_tab + (size_t)(hok ? hid : 0) * D + 8 * kc;
+    float4 h0 = f4_ld(hsrc), h1 = f4_ld(hsrc + 4);
+    const unsigned long long qb = __ballot(cq < Q && qid_l != wpad);
+    const int cnt = __popc((uint32_t)(lane < 32 ? qb : (qb >> 32)));
+    if (b == 0 && tid == 0 && e.clear_word) { e.clear_word[0] = 0u; e.clear_word[1] = 0u; e.clear_word[2] = 0u; e.clear_word[3] = 0u; }
+    // waves 0 and 1, under the requests: the FS dropout multipliers of the 128 columns (they do not depend on the data)
+    if (wave < 2) dms[tid] = drop_mult(dfs, (uint32_t)b, (uint32_t)tid);
+    vm = w1_valid_ids(S, a.P, lane, uil, L.sp[wave]);
+    KVQ_STAMP(1);                                                      // valid list known
+    PIN4(wr); PIN4(h0); PIN4(h1);                                      // (the rows arrive HERE, not beneath the tests below: DESIGN.md 5f)
+    // the linear_query rows, f_W's bias and pe[0], used behind the second barrier: requested now, where the gathered rows retire
+#pragma unroll
+    for (int u = 0; u < 8; ++u) wq[u] = f4_ld(g.wq + (size_t)(gq + 16 * u) * D + 4 * cq);
+    const float bql = g.bq[gq + 16 * (cq & 7)];                        // lane u of the group holds the bias of output gq + 16 u
+    const float4 fsb4 = f4_ld(e.fs_b + 4 * cq), pe0 = f4_ld(e.pe + 4 * cq);
+    // masked mean, part 1: embed_fwd_kernel's eight row groups add rows rg, rg + 8, ... to 0; group gq holds row gq
+    f4_st(red + gq * D + 4 * cq, make_float4(qok ? 0.f + wr.x : 0.f, qok ? 0.f + wr.y : 0.f, qok ? 0.f + wr.z : 0.f, qok ? 0.f + wr.w : 0.f));
+    {   // history row (+ pe[1 + l]; zero row for a padded id) -> x and the planes
+      float v[8] = {hok ? h0.x : 0.f, hok ? h0.y : 0.f, hok ? h0.z : 0.f, hok ? h0.w : 0.f,
+                    hok ? h1.x : 0.f, hok ? h1.y : 0.f, hok ? h1.z : 0.f, hok ? h1.w : 0.f};
+      v[0] += pr0.x; v[1] += pr0.y; v[2] += pr0.z; v[3] += pr0.w; v[4] += pr1.x; v[5] += pr1.y; v[6] += pr1.z; v[7] += pr1.w;
+      float* xd = e.x + ((size_t)b * S + rc) * D + 8 * kc;
+      f4_st(xd, make_float4(v[0], v[1], v[2], v[3]));
+      f4_st(xd + 4, make_float4(v[4], v[5], v[6], v[7]));
+      const bool on = row >= 1 && row < S;
+      const float pv[8] = {on ? v[0] : 0.f, on ? v[1] : 0.f, on ? v[2] : 0.f, on ? v[3] : 0.f,
+                           on ? v[4] : 0.f, on ? v[5] : 0.f, on ? v[6] : 0.f, on ? v[7] : 0.f};
+      put8(L.Xa, row, 8 * kc, pv);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // the word rows and the multipliers are in LDS
+    // masked mean, part 2 (every group, for its own 4 columns): row groups 0..7 in order, each (0 + row r) + row r + 8
+    float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const float4 lo = f4_ld(red + r * D + 4 * cq), hi = f4_ld(red + (r + 8) * D + 4 * cq);
+      float4 t4 = lo;
+      t4.x += hi.x; t4.y += hi.y; t4.z += hi.z; t4.w += hi.w;
+      sm.x += t4.x; sm.y += t4.y; sm.z += t4.z; sm.w += t4.w;
+      if (r & 1) __builtin_amdgcn_sched_barrier(0);                    // (all 16 reads at once are 64 registers the prologue does not have)
+    }
+    const float inv = 1.f / (float)(cnt > 0 ? cnt : 1);
+    const float4 dm4 = f4_ld(dms + 4 * cq);
+    float m[4] = {sm.x * inv, sm.y * inv, sm.z * inv, sm.w * inv};
+    m[0] *= dm4.x; m[1] *= dm4.y; m[2] *= dm4.z; m[3] *= dm4.w;
+    const float4 mv = make_float4(m[0], m[1], m[2], m[3]);
+    if (gq == 0) f4_st(e.qmean_d + (size_t)b * D + 4 * cq, mv);
+    // FS projection: out[o] = sum_i fs_w[o][i] * mean[i]
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float4 wv = fsw[u];
+      const float sdot = half_sum_last(wv.x * mv.x + wv.y * mv.y + wv.z * mv.z + wv.w * mv.w);
+      if (cq == 31) out_s[gq + 16 * u] = sdot;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { wraw[t][0] = f4_ld(wrow + 16 * t); wraw[t][1] = f4_ld(wrow + 16 * t + 4); }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // the projection is in LDS
+    float4 y = f4_ld(out_s + 4 * cq);
+    y.x = tanh_fast(y.x + fsb4.x); y.y = tanh_fast(y.y + fsb4.y); y.z = tanh_fast(y.z + fsb4.z); y.w = tanh_fast(y.w + fsb4.w);
+    x0 = y;
+    x0.x += pe0.x; x0.y += pe0.y; x0.z += pe0.z; x0.w += pe0.w;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) bqv[u] = __shfl(bql, (lane & 32) + u, 64);
+    if (gq == 0) {                                                     // query_emb, row 0 of x, row 0 of the planes
+      f4_st(e.query_emb + (size_t)b * D + 4 * cq, y);
+      f4_st(e.x + (size_t)b * S * D + 4 * cq, x0);
+      put4<X3_ROWS>(L.Xa, 0, 4 * cq, x0);
+    }
+  }
   const int Sv = __popcll(vm);
-  const int nb = wave & 3, f0 = 32 * nb + 16 * h;
   // Q while the planes settle
-  KVQ_STAMP(1);                                                        // valid list known (the first full wait)
+  if constexpr (!FRONT) KVQ_STAMP(1);                                  // valid list known (the first full wait)
   // (no global load or store under the lane test: each would be a round trip of its own behind a full wait)
   float qv[8];
 #pragma unroll
@@ -804,7 +923,8 @@ __global__ __launch_bounds__(512, 2) void kvq_attn_fwd_kernel(const KvqArgs g) {
     for (int u = 0; u < 8; ++u) L.qs[gq + 16 * u] = qv[u];
   }
   KVQ_STAMP(2);
-  __syncthreads();                                                     // planes + q in LDS
+  if constexpr (FRONT) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  else __syncthreads();                                                // planes + q in LDS
   KVQ_STAMP(3);
   if (tid < D) g.qp[(size_t)b * D + tid] = L.qs[tid];
   // ---- K / V tile of this wave: [32 features x 32 positions] over k = 128
@@ -821,8 +941,17 @@ __global__ __launch_bounds__(512, 2) void kvq_attn_fwd_kernel(const KvqArgs g) {
     for (int t = 0; t < 8; ++t) {
       uint4 bq[3];
       read_b(bq, L.Xa, l31, 16 * t + 8 * h);
-      x3_mma(acc, wf[t & 3], bq);
-      if (t < 4) load_frag(wf[t], stream, t + 4, lane);
+      if constexpr (FRONT) {
+        const float4 c0 = wraw[t & 3][0], c1 = wraw[t & 3][1];
+        const float wv8[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+        uint4 af[3];
+        split8(wv8, af);                                               // wsplit_chunk's split: the fragment's bits
+        x3_mma(acc, af, bq);
+        if (t < 4) { wraw[t][0] = f4_ld(wrow + 16 * (t + 4)); wraw[t][1] = f4_ld(wrow + 16 * (t + 4) + 4); }
+      } else {
+        x3_mma(acc, wf[t & 3], bq);
+        if (t < 4) load_frag(wf[t], stream, t + 4, lane);
+      }
       __builtin_amdgcn_sched_barrier(0);       // keep the refill where it is issued (x3frag.h, load_frag)
     }
 #pragma unroll
@@ -910,6 +1039,39 @@ __global__ __launch_bounds__(512, 2) void kvq_attn_fwd_kernel(const KvqArgs g) {
     for (int q = 0; q < 8; ++q) g.stamp[8 * (size_t)blockIdx.x + q] = kvq_st[q];
 #endif
 }
+template <int MAXK>
+__global__ __launch_bounds__(512, 2) void kvq_attn_fwd_kernel(const KvqArgs g) {      // <= 128 registers: two workgroups per CU, every sequence resident
+  extern __shared__ float kvq_lds_raw[];
+  if ((int)blockIdx.x >= g.at.n_in) {  // the backward-only weight streams are re-split here, under the sequences' workgroups (KvqArgs::split)
+    wsplit_chunk(g.split, 1, ((int)blockIdx.x - g.at.n_in) * 512 + (int)threadIdx.x);
+    return;
+  }
+  kvq_sequence_wg<MAXK, false>(g, NoFront(), *reinterpret_cast<KvqLds*>(kvq_lds_raw));
+}
+// The whole forward front end of the one-layer d = 128 step as ONE launch: a sequence's workgroup embeds, projects and attends
+// (kvq_sequence_wg<.., true>); behind the sequences ride what rode in the embed launch (embed_riders.h) — a workgroup runs TWO of
+// those 256-thread blocks side by side, and each kind's block count is padded to even so that both halves of a workgroup do the
+// same kind (they share its __syncthreads) — and both sets of the weight re-split, without fwd_kv, which nothing reads here.
+// EmbedArgs::{list,word,samp,split}_wgs count WORKGROUPS of this launch, in that order behind the sequences.
+template <int MAXK>
+__global__ __launch_bounds__(512, 4) void front_attn_fwd_kernel(const KvqArgs g, const EmbedArgs e) {      // (4 waves per SIMD = two workgroups per CU: 118 registers, no scratch)
+  extern __shared__ float kvq_lds_raw[];
+  const int r = (int)blockIdx.x - g.at.n_in;
+  if (r >= 0) {
+    const int tid = threadIdx.x, half = tid >> 8, vt = tid & 255;
+    if (r < e.list_wgs) embed_list_rows(e, 2 * r + half, vt, reinterpret_cast<int*>(kvq_lds_raw) + 4 * half);
+    else if (r < e.list_wgs + e.word_wgs) word_tasks_wg(e.sc, 2 * (r - e.list_wgs) + half, vt, kvq_lds_raw + 16 * half);
+    else if (r < e.list_wgs + e.word_wgs + e.samp_wgs) embed_sample_draw(e, (r - e.list_wgs - e.word_wgs) * 512 + tid);
+    else {
+      const int q = (r - e.list_wgs - e.word_wgs - e.samp_wgs) * 512 + tid;
+      const int n0 = wsplit_chunks(e.split, 0) - (e.split.wkv[0] ? 2 * 128 * 128 / 8 : 0);      // set 0 without fwd_kv (its last chunks)
+      if (q < n0) wsplit_chunk(e.split, 0, q);
+      else wsplit_chunk(e.split, 1, q - n0);
+    }
+    return;
+  }
+  kvq_sequence_wg<MAXK, true>(g, e, *reinterpret_cast<KvqLds*>(kvq_lds_raw));
+}
 bool kvq_attn_fits(const AttnArgs& a) {
   static const bool on = ps_env_int("PS_KVQ_FUSED", 1) != 0;
   return on && a.Sq == 1 && a.qpos == 0 && a.H == 8 && a.d == 128 && a.dh == 16 && a.S <= 32 && a.fan >= 4 && a.fan <= 24 &&
@@ -934,6 +1096,53 @@ int launch_kvq_attn_fwd(const KvqArgs& g, hipStream_t st) {
   } else {
     if (!attr32) { PS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kvq_attn_fwd_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(KvqLds))); attr32 = true; }
     hipLaunchKernelGGL((kvq_attn_fwd_kernel<8>), dim3(g.at.n_in + riders), dim3(512), sizeof(KvqLds), st, gl);
+  }
+  PS_LAUNCH_CHECK();
+  return PS_OK;
+}
+
+// The shapes the fused front end serves on top of kvq_attn_fits: the TEM sequence with the FS query encoder projected in the
+// launch, positional rows, the row list, and at most 16 query words (one per lane group of the sequence's workgroup; longer
+// queries keep the two launches).  The AVG encoder keeps the two launches as well.
+bool front_attn_fits(const AttnArgs& a, const EmbedArgs& e) {
+  return kvq_attn_fits(a) && e.tem && e.fs && e.use_pos && e.d == 128 && e.Q >= 1 && e.Q <= PS_FRONT_MAX_Q && e.L + 1 == a.S &&
+         e.B == a.n_in && !e.zero_i32;
+}
+int launch_front_attn_fwd(const KvqArgs& g, const EmbedArgs& e, hipStream_t st) {
+  PS_REQUIRE(front_attn_fits(g.at, e), "fused front end: unsupported shape");
+  PS_REQUIRE(g.wkv[0] && g.wkv[1] && g.bk && g.bv && g.wq && g.bq && g.kp && g.vp && g.qp && g.amask && g.at.attn && g.at.ctx && g.at.ui,
+             "fused front end: null pointer (projection + attention)");
+  PS_REQUIRE(e.qw && e.ui && e.ui == g.at.ui && e.word_emb && e.hist_tab && e.pe && e.fs_w && e.fs_b && e.qmean_d && e.query_emb && e.x &&
+             e.vrows && e.vcount, "fused front end: null pointer (embed)");
+  PS_REQUIRE(!e.fold_words || (e.sc.word_blk && e.sc.ticket && e.sc.d <= 512), "fused front end: folded word tasks need their buffers");
+  EmbedArgs b = e;
+  b.list_wgs = ps_cdiv(e.B, 2);
+  b.word_wgs = e.fold_words ? ps_cdiv(e.sc.word_nblk, 2) : 0;
+  b.samp_wgs = e.samp_prob ? ps_cdiv(e.samp_nitem + e.samp_nword, 512) : 0;
+  b.split_wgs = 0; b.zero_wgs = 0;
+  if (e.split.on) {
+    const WSplit& W = e.split;
+    PS_REQUIRE(W.w[0] && W.w[1] && W.w[2] && W.fwd_wo && W.fwd_ff && W.bwd_ff && W.bwd_wo && W.wkv[0] && W.wkv[1] && W.bwd_kv,
+               "fused front end: weight split: null pointer");
+    PS_REQUIRE(W.rows[0] == 128 && W.cols[0] == 128 && W.cols[1] == 128 && W.rows[2] == 128 && W.rows[1] == W.cols[2] &&
+               W.rows[1] % 256 == 0, "fused front end: weight split: shapes");
+    b.split_wgs = ps_cdiv(2 * wsplit_chunks(W, 0) - 2 * 128 * 128 / 8, 512);       // set 0 without fwd_kv, then set 1
+  }
+  const int riders = b.list_wgs + b.word_wgs + b.samp_wgs + b.split_wgs;
+#if PS_DIAG_ON
+  KvqArgs gd = g;
+  gd.stamp = ps_diag_int("PS_KVQ_STAMP", 0) ? ps_debug_stamp_ptr() : nullptr;
+  const KvqArgs& gl = gd;
+#else
+  const KvqArgs& gl = g;
+#endif
+  static bool attr24 = false, attr32 = false;
+  if (g.at.S <= 24) {
+    if (!attr24) { PS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(front_attn_fwd_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(KvqLds))); attr24 = true; }
+    hipLaunchKernelGGL((front_attn_fwd_kernel<6>), dim3(g.at.n_in + riders), dim3(512), sizeof(KvqLds), st, gl, b);
+  } else {
+    if (!attr32) { PS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(front_attn_fwd_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(KvqLds))); attr32 = true; }
+    hipLaunchKernelGGL((front_attn_fwd_kernel<8>), dim3(g.at.n_in + riders), dim3(512), sizeof(KvqLds), st, gl, b);
   }
   PS_LAUNCH_CHECK();
   return PS_OK;

@@ -47,6 +47,7 @@ enum AttnForm {
 struct EncPlan {
   AttnForm attn[PS_MAX_LAYERS];
   bool rowlist;             // the (one-layer) encoder walks the valid-row list: padded rows of x are read nowhere, need not be written
+  bool front_fused;         // ATTN_KVQ whose launch embeds the sequences too (front_attn_fwd_kernel): no embed launch; ps_set_front_fused
   bool fwd_fuse_last;       // last layer's Wo + LN + FFN + final LN as one forward kernel (mlp_fused.hip)
   bool fold_score;          // ... whose epilogue can take item scoring + loss (ScoreArgs, folded form)
   struct Bwd {
@@ -79,6 +80,7 @@ struct EncFwdOpts {
   bool rows_listed = false;            // as for enc_plan; the K/V products of a one-layer encoder then run over those rows only
   const ScoreArgs* fold_sc = nullptr;  // TEM with replicas: item scoring + loss run in the epilogue of the last layer's fused kernel
   bool split_bwd_left = false;         // the embed launch left the backward-only weight streams to the fused projection + attention launch
+  const EmbedArgs* front = nullptr;    // EncPlan::front_fused: the embed launch's arguments — NOT launched by the caller; layer 0's launch does its work
 };
 int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
                        const Ws& w, hipStream_t st, const EncFwdOpts& o);

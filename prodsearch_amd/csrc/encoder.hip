@@ -283,6 +283,12 @@ int enc_final_ln_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, c
   return PS_OK;
 }
 
+// The embed launch inside the projection + attention launch (front_attn_fwd_kernel, attn_sq1.hip): PS_FRONT_FUSED=0 /
+// ps_set_front_fused(0) restores the two launches; PS_KVQ_FUSED=0 implies it (the form is the kvq form's).
+static int& front_fused_slot() { static int v = ps_env_int("PS_FRONT_FUSED", 1); return v; }
+extern "C" int ps_set_front_fused(int on) { return std::exchange(front_fused_slot(), on); }
+static int g_front_taken = 0;                  // the last forward launched it (ps_front_fused_taken; PsEncPath has no field for it)
+extern "C" int ps_front_fused_taken(void) { return g_front_taken; }
 int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
                        const Ws& w, hipStream_t st, const EncFwdOpts& o) {
   const int d = D.d, S = w.S, NL = D.n_layers;
@@ -306,6 +312,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
     a.kp = ws + l.kp; a.vp = ws + l.vp; a.qp = ws + l.qp; a.attn = ws + l.attn; a.ctx = ws + l.ctx;
     a.drop = make_drop(D, PS_SITE_ATTN(i));
     uint32_t* amask = reinterpret_cast<uint32_t*>(ws + l.amask);
+    PS_REQUIRE(!o.front == !pl.front_fused, "forward: the caller and the plan disagree about the embed launch");
     if (pl.attn[i] == ATTN_KVQ) {
       const WSplit kvs = make_wsplit(D, P, ws, w);
       KvqArgs q;
@@ -314,7 +321,11 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       q.at = a; q.x = xn; q.kv_stream = kvs.fwd_kv;
       q.bk = Lp.bk; q.bv = Lp.bv; q.wq = Lp.wq; q.bq = Lp.bq;
       q.kp = ws + l.kp; q.vp = ws + l.vp; q.qp = ws + l.qp; q.amask = amask;
-      TRY(launch_kvq_attn_fwd(q, st));
+      if (pl.front_fused) {                          // ... and the embed launch's work (its caller did not launch it)
+        q.wkv[0] = Lp.wk; q.wkv[1] = Lp.wv;
+        TRY(launch_front_attn_fwd(q, *o.front, st));
+        g_front_taken = 1;
+      } else TRY(launch_kvq_attn_fwd(q, st));
       tk.attn[i] = ATTN_KVQ; tk.rowlist = 1;         // (its workgroups project their sequence's valid positions only)
     } else {   // K, V, Q projections (neural.py:192-197), Q pre-divided by sqrt(dh) (:206)
       GemmGroup g;
@@ -378,6 +389,7 @@ PsEncPath& enc_taken(int backward) { return g_taken[backward ? 1 : 0]; }
 void enc_taken_clear(int backward, int n_layers) {
   PsEncPath& t = enc_taken(backward);
   memset(&t, 0, sizeof(t));
+  if (!backward) g_front_taken = 0;
   t.n_layers = n_layers;
 }
 extern "C" int ps_item_scatter_fused_taken(void) { return g_taken[1].item_scatter; }
@@ -415,7 +427,12 @@ EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws&
   pl.rowlist = rows_on && rows_listed && NL == 1 && w.qpos == 0 && w.vrows != 0 && l0.n_in == D.B && sq1;
   // One layer, replicas, d = 128: projections + attention of the one consumed position in ONE launch, a workgroup per
   // sequence (kvq_attn_fwd_kernel): the K / V weight fragments were re-split by the embed launch in front (WSplit::fwd_kv)
+  // (the streams must exist either way: ps_set_front_fused can restore that launch from one call to the next)
   if (NL == 1 && kvs.on && kvs.fwd_kv && ps_fusion_enabled() && pl.rowlist && wf && kvq_attn_fits(a0) && l0.amask) pl.attn[0] = ATTN_KVQ;
+  // ... and the embed launch in front of it as well (front_attn_fwd_kernel): FS query encoder (projected in the launch), positional
+  // rows, at most PS_FRONT_MAX_Q query words; the AVG encoder and longer queries keep the two launches
+  pl.front_fused = pl.attn[0] == ATTN_KVQ && front_fused_slot() != 0 && D.query_encoder == PS_QENC_FS && D.use_pos_emb &&
+                   D.Q >= 1 && D.Q <= PS_FRONT_MAX_Q && P.fs_w && P.fs_b && P.pe && kvs.bwd_kv;
   const bool last_fusable = ps_fusion_enabled() && ll.Sq == 1 && mlp_fused_serves(d, D.F) && w.wsplit;
   pl.fwd_fuse_last = last_fusable && P.final_ln_g && P.final_ln_b;
   // Folded scoring (ScoreArgs): TEM training forward with replicas whose last layer takes the wave-specialised fused form

@@ -79,7 +79,8 @@ struct WSplit {
 // One thread = one 16-byte fragment chunk (8 reduction elements of one weight row) of one product step, all three planes.
 // The streams form two SETS: 0 = what the forward's later launches read (fwd_wo, fwd_ff, fwd_kv), 1 = what only the backward
 // reads (bwd_ff, bwd_wo, bwd_kv).  Set 0 rides in the embed launch; set 1 rides in the launch behind it when that is the fused
-// projection + attention kernel (KvqArgs::split), else in the embed launch too.
+// projection + attention kernel (KvqArgs::split), else in the embed launch too.  The fused front end (front_attn_fwd_kernel) carries
+// both sets without fwd_kv: its waves split the fp32 K / V rows in registers.
 __host__ __device__ inline int wsplit_chunks(const WSplit& W, int /*set: both sets have the same size*/) {
   const int d = W.cols[0], F = W.rows[1];
   return (d * d + 2 * d * F) / 8 + (W.wkv[0] ? 2 * d * d / 8 : 0);
@@ -255,6 +256,7 @@ struct KvqArgs {
   AttnArgs at;
   const float* x;
   const uint16_t* kv_stream;
+  const float* wkv[2];           // fused front end only: linear_keys / linear_values themselves (kv_stream is then not read)
   const float* bk; const float* bv; const float* wq; const float* bq;
   float* kp; float* vp; float* qp;
   uint32_t* amask;
@@ -263,6 +265,11 @@ struct KvqArgs {
 };
 bool kvq_attn_fits(const AttnArgs& a);     // d = 128, 8 heads, <= 32 positions, 4..24 replicas, query position 0
 int launch_kvq_attn_fwd(const KvqArgs& a, hipStream_t st);
+// ... and the embed launch in front of it too (attn_sq1.hip, front_attn_fwd_kernel): `e` as for launch_embed_fwd, whose
+// sequences' work the workgroups do themselves and whose riders follow them; x, qmean_d and query_emb are still written.
+#define PS_FRONT_MAX_Q 16
+bool front_attn_fits(const AttnArgs& a, const EmbedArgs& e);   // kvq_attn_fits + TEM, FS encoder, positional rows, Q <= PS_FRONT_MAX_Q
+int launch_front_attn_fwd(const KvqArgs& a, const EmbedArgs& e, hipStream_t st);
 // last-layer form (Sq == 1): one workgroup per sequence, all heads, replicas share K/V in LDS (attn_sq1.hip)
 int launch_attn_fwd_sq1(const AttnArgs& a, hipStream_t st);
 int launch_attn_bwd_sq1(const AttnArgs& a, hipStream_t st);

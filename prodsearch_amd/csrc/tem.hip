@@ -12,6 +12,8 @@
 #include "side_stream.h"
 #include "wgrad.h"
 #include <string.h>
+#include <math.h>
+#include <vector>
 
 // -------------------------------------------------------------- encoder forward
 struct SamplerArgs { const float* prob; const int32_t* alias; int64_t* items; int64_t* words; };
@@ -55,8 +57,14 @@ static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTem
   e.split = make_wsplit(D, P, ws, w);
   EncFwdOpts o;
   o.rows_listed = rows_list_ok(D); o.fold_sc = fold_sc;
+  const EncPlan pl = enc_plan(D, P, ws, w, o.rows_listed, nullptr);
+  if (tem && pl.front_fused) {                   // one launch embeds, projects and attends: layer 0's (enc_layers_forward)
+    PS_REQUIRE(fs_fused && e.vrows, "forward: the fused front end needs the FS projection and the row list");
+    o.front = &e;
+    return enc_layers_forward(D, P, Bt.u_item_idxs, nullptr, ws, w, st, o);
+  }
   // the fused projection + attention launch re-splits the backward's streams
-  o.split_bwd_left = e.split.on && D.training && enc_plan(D, P, ws, w, o.rows_listed, nullptr).attn[0] == ATTN_KVQ;
+  o.split_bwd_left = e.split.on && D.training && pl.attn[0] == ATTN_KVQ;
   e.split_fwd_only = o.split_bwd_left ? 1 : 0;
   TRY(launch_embed_fwd(e, st));
   if (e.fs && !fs_fused) {   // FSEncoder: tanh(f_W . mean + b)  (text_encoder.py:39); also writes row 0 of x (+pe[0])
@@ -150,6 +158,96 @@ extern "C" int ps_tem_forward_sampled(const PsTemDesc* desc, const PsTemTensors*
   TRY(encode_forward(D, *params, Bt, workspace, w, st, &samp));
   TRY(launch_score_fwd(s, st));
   TRY(launch_loss(s, st));
+  return PS_OK;
+}
+
+// Unit-test hook (prodsearch_hip.h): the forward with the embed launch in front (ws_a) and inside the projection + attention
+// launch (ws_b), region by region.  Host-side comparison of copies: a test entry, not a step.
+extern "C" int ps_set_front_fused(int on);
+extern "C" int ps_front_fused_taken(void);
+extern "C" int ps_front_fused_test(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch, const float* alias_prob,
+                                   const int32_t* alias_idx, float* ws_a, float* ws_b, int64_t* neg_item_a, int64_t* neg_word_a,
+                                   int64_t* neg_item_b, int64_t* neg_word_b, float* loss3_a, float* loss3_b, double* diff,
+                                   int32_t* taken, ps_stream_t stream) {
+  PS_REQUIRE(desc && params && batch && ws_a && ws_b && diff && taken && batch->u_item_idxs, "front_fused_test: null argument");
+  const PsTemDesc& D = *desc;
+  PS_REQUIRE(D.model == PS_MODEL_TEM && D.n_layers >= 1, "front_fused_test: an item-transformer step with encoder layers");
+  Ws w;
+  TRY(make_ws(D, w));
+  hipStream_t st = (hipStream_t)stream;
+  const int old = ps_set_front_fused(0);
+  int rc = ps_tem_forward_sampled(desc, params, batch, alias_prob, alias_idx, neg_item_a, neg_word_a, ws_a, loss3_a, nullptr, stream);
+  taken[0] = ps_front_fused_taken();
+  if (rc == PS_OK) {
+    ps_set_front_fused(1);
+    rc = ps_tem_forward_sampled(desc, params, batch, alias_prob, alias_idx, neg_item_b, neg_word_b, ws_b, loss3_b, nullptr, stream);
+    taken[1] = ps_front_fused_taken();
+  }
+  ps_set_front_fused(old);
+  TRY(rc);
+  PS_CHECK_HIP(hipStreamSynchronize(st));
+  const int B = D.B, S = w.S, d = D.d, L = D.L;
+  const LayerWs& l0 = w.layer[0];
+  std::vector<int64_t> ui((size_t)B * L);
+  PS_CHECK_HIP(hipMemcpy(ui.data(), batch->u_item_idxs, ui.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> ha, hb;
+  // words [off, off + n) of both workspaces -> ha / hb
+  auto fetch = [&](const void* pa, const void* pb, size_t n) -> int {
+    ha.resize(n); hb.resize(n);
+    if (n == 0) return PS_OK;
+    PS_CHECK_HIP(hipMemcpy(ha.data(), pa, n * 4, hipMemcpyDeviceToHost));
+    PS_CHECK_HIP(hipMemcpy(hb.data(), pb, n * 4, hipMemcpyDeviceToHost));
+    return PS_OK;
+  };
+  auto fdiff = [&](size_t i) -> double {          // as floats
+    if (ha[i] == hb[i]) return 0.0;
+    float x, y;
+    memcpy(&x, &ha[i], 4); memcpy(&y, &hb[i], 4);
+    const double e = fabs((double)x - (double)y);
+    return e == e ? e : INFINITY;
+  };
+  auto region_f = [&](int64_t off, size_t n, double& out) -> int {
+    TRY(fetch(ws_a + off, ws_b + off, n));
+    out = 0.0;
+    for (size_t i = 0; i < n; ++i) out = fmax(out, fdiff(i));
+    return PS_OK;
+  };
+  auto region_i = [&](const void* pa, const void* pb, size_t n, double& out) -> int {   // as int32 words
+    TRY(fetch(pa, pb, n));
+    out = 0.0;
+    for (size_t i = 0; i < n; ++i) out = fmax(out, fabs((double)(int32_t)ha[i] - (double)(int32_t)hb[i]));
+    return PS_OK;
+  };
+  for (int r = 0; r < PS_FRONT_TEST_REGIONS; ++r) diff[r] = 0.0;
+  TRY(region_f(w.x, (size_t)B * S * d, diff[0]));
+  TRY(region_f(w.qmean, (size_t)B * d, diff[1]));
+  TRY(region_f(w.query_emb, (size_t)B * d, diff[2]));
+  for (int kv = 0; kv < 2; ++kv) {                 // K / V rows exist at valid positions only
+    TRY(fetch(ws_a + (kv ? l0.vp : l0.kp), ws_b + (kv ? l0.vp : l0.kp), (size_t)l0.n_in * S * d));
+    if (l0.n_in != B || w.qpos != 0) continue;     // (other layouts: nothing to say about which rows are written)
+    for (int b = 0; b < B; ++b)
+      for (int s2 = 0; s2 < S; ++s2) {
+        if (s2 > 0 && ui[(size_t)b * L + s2 - 1] == D.product_size) continue;
+        for (int c = 0; c < d; ++c) diff[3 + kv] = fmax(diff[3 + kv], fdiff(((size_t)b * S + s2) * d + c));
+      }
+  }
+  TRY(region_f(l0.qp, (size_t)l0.n_in * l0.Sq * d, diff[5]));
+  TRY(region_f(l0.attn, (size_t)l0.n_in * D.H * l0.Sq * S, diff[6]));
+  if (l0.amask) TRY(region_i(ws_a + l0.amask, ws_b + l0.amask, (size_t)l0.n_in * l0.fan * D.H, diff[7]));
+  TRY(region_f(l0.ctx, (size_t)l0.M2 * d, diff[8]));
+  TRY(region_f(w.word_scores, (size_t)B * D.W * (D.K + 1), diff[9]));
+  TRY(region_f(w.word_terms, (size_t)B * D.W * (D.K + 1), diff[10]));
+  TRY(region_i(neg_item_a, neg_item_b, (size_t)2 * B * D.K, diff[11]));
+  TRY(region_i(neg_word_a, neg_word_b, (size_t)2 * B * D.W * D.K, diff[12]));
+  if (w.vrows) {
+    int32_t ca = 0, cb = 0;
+    PS_CHECK_HIP(hipMemcpy(&ca, ws_a + w.vcount, 4, hipMemcpyDeviceToHost));
+    PS_CHECK_HIP(hipMemcpy(&cb, ws_b + w.vcount, 4, hipMemcpyDeviceToHost));
+    diff[14] = fabs((double)ca - (double)cb);
+    const int n = ca < cb ? ca : cb;
+    PS_REQUIRE(n >= 0 && n <= B * S, "front_fused_test: row count %d / %d out of range", ca, cb);
+    TRY(region_i(ws_a + w.vrows, ws_b + w.vrows, (size_t)n, diff[13]));
+  }
   return PS_OK;
 }
 

@@ -26,7 +26,7 @@ first = sys.argv[3] if len(sys.argv) > 3 else None
 names = (first,) if first else ('sample_kernel', 'tem_stage_kernel')
 idx = [i for i, r in enumerate(rows) if any(n in r[2] for n in names)]
 if len(idx) < 2:      # sampling folded into the first kernel of the step
-    idx = [i for i, r in enumerate(rows) if 'embed_fwd_kernel' in r[2]]
+    idx = [i for i, r in enumerate(rows) if 'embed_fwd_kernel' in r[2] or 'front_attn_fwd_kernel' in r[2]]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else len(idx) // 2
 s, e = idx[k], idx[k + 1]
 t0 = rows[s][0]
