@@ -270,7 +270,8 @@ static AeAttnArgs ae_args(const PsTemDesc& D, const int64_t* ui, float* ws, cons
 }
 
 // forward: reads w.query_emb, writes w.enc [B*R, d]
-int ae_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, float* ws, const Ws& w, hipStream_t st) {
+int ae_forward(const EncCall& c) {
+  const PsTemDesc& D = c.D; const PsTemTensors& P = c.P; const int64_t* ui = c.ui; float* ws = c.ws; const Ws& w = c.w; hipStream_t st = c.st;
   const PsLayerTensors& A = P.layer[0];
   PS_REQUIRE(ui, "forward: null u_item_idxs");
   PS_REQUIRE(A.wk && A.bk && A.wv && A.bv && A.wq && A.bq && A.wo && A.bo, "forward: null attention_encoder tensors (layer[0])");
@@ -308,8 +309,8 @@ int ae_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, flo
 
 // backward: reads w.denc (d out, [B*R,d]); accumulates the attention_encoder gradients into G.layer[0] and the history rows'
 // into the history table; leaves d query_emb in w.ae_dqe [B,d]
-int ae_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui, float* ws, const Ws& w,
-                hipStream_t st) {
+int ae_backward(const EncCall& call, const PsTemTensors& G) {
+  const PsTemDesc& D = call.D; const PsTemTensors& P = call.P; const int64_t* ui = call.ui; float* ws = call.ws; const Ws& w = call.w; hipStream_t st = call.st;
   const PsLayerTensors& A = P.layer[0];
   const PsLayerTensors& GA = G.layer[0];
   PS_REQUIRE(ui, "backward: null u_item_idxs");

@@ -1,5 +1,5 @@
 // encoder.h — the transformer encoder shared by the item models (tem.hip) and the review transformer (rtm.hip), implemented in
-// encoder.hip: the workspace layout, the per-call plan and the layer loops (forward / backward).
+// encoder.hip: the workspace layout, the per-call context with its plan (EncCall) and the layer loops (forward / backward).
 #pragma once
 #include "rowwise.h"
 
@@ -35,8 +35,8 @@ WSplit make_wsplit(const PsTemDesc& D, const PsTemTensors& P, float* ws, const W
 int wplane_list(const PsTemDesc& D, const PsTemTensors& P, const Ws& w, const float** ws_, int* rows, int* cols);
 
 // ------------------------------------------------------------- one plan per call
-// Which path every step of the encoder takes, decided once per call by enc_plan (host only, no launches) from the shapes, the
-// weights present and the switches; the forward, the backward and their callers read it instead of deciding again.
+// Which path every step of the encoder takes, decided by enc_plan (host only, no launches) from the shapes, the weights present
+// and the switches.  An entry point decides it ONCE, when it builds its EncCall (below); everything under it reads that copy.
 enum AttnForm {
   ATTN_GENERIC,             // any Sq (launch_attn_fwd / launch_attn_bwd)
   ATTN_SQ1,                 // one query row: a workgroup per sequence, replicas share K / V in LDS
@@ -64,34 +64,42 @@ struct EncPlan {
     bool dx_fused;          // ... or no dX product at all: the attention backward leaves d x as two partial rows
   } bwd;
 };
-// `rows_listed`: w.vrows / w.vcount hold the list of valid (non-pad) rows of x (EmbedArgs::vrows, or the review transformer's
-// rtm_rowlist_kernel).  `valid`: the key-padding mask the layer loops will get (below); null for u_item_idxs.
-// enc_plan reads which tensors of P are null and the offsets in w, and builds addresses from ws; it never dereferences a
-// tensor or ws (ps_tem_plan calls it without a device).
-EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed, const float* valid);
+
+// ------------------------------------------------------------- one context per entry call
+// EncBase: what every encoder function of a call reads.  EncCall: ... plus whose sequences these are, the plan and the weight
+// split, each made once, by enc_call.  Built per entry call and never kept: the setters may change between two calls.
+// enc_call dereferences neither a tensor nor ws (it reads which tensors are null and adds offsets: ps_tem_plan builds one over
+// stand-ins, without a device); enc_plan (encoder.hip) has no other caller.  Besides the call it reads enc_switches() — the env /
+// diag switches, read once per process, and the values ps_set_front_fused / ps_set_fuse_bwd_min / ps_set_item_scatter_fused
+// write — and ps_deterministic(), each time.
+struct EncBase { const PsTemDesc& D; const PsTemTensors& P; float* ws; const Ws& w; hipStream_t st; };
+struct EncCall : EncBase {
+  const int64_t* ui;        // key-padding mask: `valid` [n_seq, S] floats if given, else u_item_idxs != P (TEM)
+  const float* valid;
+  bool rows_listed;         // w.vrows / w.vcount hold the list of valid (non-pad) rows of x (EmbedArgs::vrows, or the review transformer's rtm_rowlist_kernel)
+  EncPlan plan;
+  WSplit x3;
+};
+EncCall enc_call(const EncBase& b, const int64_t* ui, const float* valid, bool rows_listed);
 // What the layer loops really launched (ps_enc_path_taken): one record per direction, cleared where a direction's call starts
 // and filled at the launching branches — host bookkeeping, never read by the step itself.
 PsEncPath& enc_taken(int backward);
 void enc_taken_clear(int backward, int n_layers);
 
 // All encoder layers + the final LayerNorm on the consumed position: reads w.x, writes w.enc.
-// Key-padding mask: `valid` [n_seq, S] floats if given, else u_item_idxs != P (TEM).
 struct EncFwdOpts {
-  bool rows_listed = false;            // as for enc_plan; the K/V products of a one-layer encoder then run over those rows only
   const ScoreArgs* fold_sc = nullptr;  // TEM with replicas: item scoring + loss run in the epilogue of the last layer's fused kernel
   bool split_bwd_left = false;         // the embed launch left the backward-only weight streams to the fused projection + attention launch
   const EmbedArgs* front = nullptr;    // EncPlan::front_fused: the embed launch's arguments — NOT launched by the caller; layer 0's launch does its work
 };
-int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
-                       const Ws& w, hipStream_t st, const EncFwdOpts& o);
+int enc_layers_forward(const EncCall& c, const EncFwdOpts& o);
 // The per-replica tail of layer i behind its attention, as enc_layers_forward runs it: Wo + residual -> FF LayerNorm -> W1 -> GELU
 // -> W2 + residual, reading l.ctx [l.M2, d] and the residual row (m / l.fan) * w.S + w.qpos of xin.  `fuse`: the one-kernel form of
-// the LAST layer (mlp_fused.hip: needs w.wsplit filled by an embed launch, d = 128), which also applies the final LayerNorm into
-// w.enc; otherwise the caller follows with enc_final_ln_forward.  Callers: the layer loop, and the review transformer's
-// full-catalogue ranking (rtm_rank.hip), whose "replicas" are the candidates of an entry.
-int enc_tail_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, int i, const float* xin, bool fuse,
-                     const ScoreArgs* fold_sc, hipStream_t st);
-int enc_final_ln_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, hipStream_t st);
+// the LAST layer (mlp_fused.hip: needs the streams of x3 filled by an embed launch, d = 128), which also applies the final
+// LayerNorm into w.enc; otherwise the caller follows with enc_final_ln_forward.  Callers: the layer loop, and the review
+// transformer's full-catalogue ranking (rtm_rank.hip), whose "replicas" are the candidates of an entry and which has no plan.
+int enc_tail_forward(const EncBase& b, const WSplit& x3, int i, const float* xin, bool fuse, const ScoreArgs* fold_sc);
+int enc_final_ln_forward(const EncBase& b);
 // Backward of enc_layers_forward: reads w.denc (grad wrt w.enc), accumulates parameter grads into G, writes w.dx.
 struct EncBwdIn {
   // the LayerNorm backwards park their column sums in w.lnpart and append to this list; the caller must hand it to a later
@@ -101,7 +109,6 @@ struct EncBwdIn {
   // from the scores inside that kernel and the score backward (table scatter only) is launched on the side stream behind it, off
   // the dependent chain; otherwise it is launched first, as usual
   const ScoreArgs* score_on_side = nullptr;
-  bool rows_listed = false;
   bool caller_flushes_tail = false;    // the caller launches EncBwdOut's deferred work behind its embedding scatter
 };
 struct EncBwdOut {
@@ -114,14 +121,12 @@ struct EncBwdOut {
   bool item_scatter_taken = false;     // the fused kernel scattered the item rows
 };
 void enc_record_backward(const EncBwdOut& out);   // once per backward entry point: what ps_item_scatter_fused_taken() reports (the taken record's item_scatter)
-int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui,
-                        const float* valid, float* ws, const Ws& w, hipStream_t st, const EncBwdIn& in, EncBwdOut& out);
+int enc_layers_backward(const EncCall& c, const PsTemTensors& G, const EncBwdIn& in, EncBwdOut& out);
 
 // ZAM / AEM (attn_emb.hip): the attention-embedding step between the query encoder and the scoring.  ae_forward reads
 // w.query_emb and writes w.enc [B*R,d]; ae_backward reads w.denc and leaves d query_emb in w.ae_dqe [B,d].
 #define PS_AE_COL_SPLITS 128      // row splits of ae_backward's deterministic bias column sums (w.ae_part: [4][splits][d])
 bool ps_model_attn(int model);
 int ae_zoff(const PsTemDesc& D);
-int ae_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, float* ws, const Ws& w, hipStream_t st);
-int ae_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui, float* ws, const Ws& w,
-                hipStream_t st);
+int ae_forward(const EncCall& c);
+int ae_backward(const EncCall& c, const PsTemTensors& G);

@@ -1,4 +1,4 @@
-// encoder.hip — the transformer encoder both models share (encoder.h): workspace layout, the per-call plan (enc_plan),
+// encoder.hip — the transformer encoder both models share (encoder.h): workspace layout, the per-call context and its plan (enc_call),
 // the taken-path record and the layer loops, forward and backward.  The item models (tem.hip) and the review transformer
 // (rtm.hip) call it alike.
 //
@@ -226,8 +226,8 @@ static AttnArgs attn_shape(const PsTemDesc& D, const Ws& w, int i, const int64_t
 }
 
 // Layer i's per-replica tail behind its attention (encoder.h): reads l.ctx and the residual rows of xin.
-int enc_tail_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, int i, const float* xin, bool fuse,
-                     const ScoreArgs* fold_sc, hipStream_t st) {
+int enc_tail_forward(const EncBase& b, const WSplit& x3, int i, const float* xin, bool fuse, const ScoreArgs* fold_sc) {
+  const PsTemDesc& D = b.D; const PsTemTensors& P = b.P; float* ws = b.ws; const Ws& w = b.w; hipStream_t st = b.st;
   const int d = D.d, S = w.S;
   const LayerWs& l = w.layer[i];
   const PsLayerTensors& Lp = P.layer[i];
@@ -243,7 +243,7 @@ int enc_tail_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const
     m.y1 = ws + l.y1; m.ln1 = ws + l.ln1; m.st1 = ws + l.ff_stats; m.a1 = ws + l.a1; m.h1 = ws + l.h1;
     m.y2 = ws + l.y2; m.stf = ws + w.fin_stats; m.enc = ws + w.enc;
     if (fold_sc) { m.fold_score = 1; m.sc = *fold_sc; }
-    m.x3 = make_wsplit(D, P, ws, w);
+    m.x3 = x3;
     return launch_mlp_fwd_fused(m, st);
   }
   {   // final_linear + dropout + residual (neural.py:228-231, transformer.py:56)
@@ -268,7 +268,8 @@ int enc_tail_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const
 }
 
 // final LayerNorm (transformer.py:86) on the consumed position only
-int enc_final_ln_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, hipStream_t st) {
+int enc_final_ln_forward(const EncBase& b) {
+  const PsTemDesc& D = b.D; const PsTemTensors& P = b.P; float* ws = b.ws; const Ws& w = b.w; hipStream_t st = b.st;
   const int d = D.d, S = w.S, NL = D.n_layers;
   PS_REQUIRE(P.final_ln_g && P.final_ln_b, "forward: null final LayerNorm");
   LnFwdArgs f;
@@ -283,16 +284,56 @@ int enc_final_ln_forward(const PsTemDesc& D, const PsTemTensors& P, float* ws, c
   return PS_OK;
 }
 
-// The embed launch inside the projection + attention launch (front_attn_fwd_kernel, attn_sq1.hip): PS_FRONT_FUSED=0 /
-// ps_set_front_fused(0) restores the two launches; PS_KVQ_FUSED=0 implies it (the form is the kvq form's).
-static int& front_fused_slot() { static int v = ps_env_int("PS_FRONT_FUSED", 1); return v; }
-extern "C" int ps_set_front_fused(int on) { return std::exchange(front_fused_slot(), on); }
-static int g_front_taken = 0;                  // the last forward launched it (ps_front_fused_taken; PsEncPath has no field for it)
-extern "C" int ps_front_fused_taken(void) { return g_front_taken; }
-int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t* ui, const float* valid, float* ws,
-                       const Ws& w, hipStream_t st, const EncFwdOpts& o) {
+// ---- what the plan reads besides its arguments (and ps_deterministic()): the env / diag switches, read once per process, and
+// the three values the setters write, which enc_plan reads on every call
+struct EncSwitches {
+  bool rows_on, bwd_fuse_on, dx_fused_on;      // PS_NO_ROWLIST, PS_NO_FUSE_BWD, PS_KVDX_FUSED
+  bool wgrad_early, wg3_main_on, wg3_last;     // PS_WGRAD_LATE, PS_WG3_SIDE (unset: by fork_by_kernel()), PS_WG3_LAST
+  // The embed launch inside the projection + attention launch (front_attn_fwd_kernel, attn_sq1.hip): PS_FRONT_FUSED=0 /
+  // ps_set_front_fused(0) restores the two launches; PS_KVQ_FUSED=0 implies it (the form is the kvq form's).
+  int front_fused;
+  int fuse_bwd_min;                            // PS_FUSE_BWD_MIN / ps_set_fuse_bwd_min
+  // The item rows' gradient scatter (g_product_emb[idx(b, j)] += ds * enc[(b, j)]) rides in the fused per-replica backward, which
+  // holds ds and idx already, and the score backward's launch shrinks to its word tasks (MlpBwdArgs::g_product_emb,
+  // ScoreArgs::items_elsewhere), which then are the main stream's last launch instead of the side stream's first (see
+  // bwd_fused_last).  PS_ITEM_SCATTER_FUSED=0: the score backward's own item workgroups, on the side stream, as before.
+  // Deterministic mode never takes it (its sole-owner scatter walks the item tasks in order).
+  int item_scatter_fused;
+};
+static EncSwitches& enc_switches() {
+  static const int wg3_side = ps_diag_int("PS_WG3_SIDE", -1);
+  static EncSwitches s = {ps_env_int("PS_NO_ROWLIST", 0) == 0, ps_env_int("PS_NO_FUSE_BWD", 0) == 0, ps_env_int("PS_KVDX_FUSED", 1) != 0,
+                          ps_diag_int("PS_WGRAD_LATE", 0) == 0, wg3_side >= 0 ? wg3_side == 0 : fork_by_kernel(), ps_diag_int("PS_WG3_LAST", 1) != 0,
+                          ps_env_int("PS_FRONT_FUSED", 1), ps_env_int("PS_FUSE_BWD_MIN", 1024), ps_env_int("PS_ITEM_SCATTER_FUSED", 1)};
+  return s;
+}
+extern "C" int ps_set_front_fused(int on) { return std::exchange(enc_switches().front_fused, on); }
+extern "C" int ps_set_fuse_bwd_min(int rows) { return std::exchange(enc_switches().fuse_bwd_min, rows); }
+extern "C" int ps_set_item_scatter_fused(int on) { return std::exchange(enc_switches().item_scatter_fused, on); }
+
+// What the last forward [0] / backward [1] launched (encoder.h, enc_taken); item_scatter: the fused kernel scattered the item rows.
+// front: the last forward embedded inside layer 0's launch (ps_front_fused_taken; PsEncPath has no field for it)
+static struct { PsEncPath path[2]; int front; } g_taken;
+PsEncPath& enc_taken(int backward) { return g_taken.path[backward ? 1 : 0]; }
+void enc_taken_clear(int backward, int n_layers) {
+  PsEncPath& t = enc_taken(backward);
+  memset(&t, 0, sizeof(t));
+  if (!backward) g_taken.front = 0;
+  t.n_layers = n_layers;
+}
+extern "C" int ps_front_fused_taken(void) { return g_taken.front; }
+extern "C" int ps_item_scatter_fused_taken(void) { return g_taken.path[1].item_scatter; }
+void enc_record_backward(const EncBwdOut& out) { g_taken.path[1].item_scatter = out.item_scatter_taken ? 1 : 0; }
+extern "C" int ps_enc_path_taken(int32_t backward, PsEncPath* out) {
+  PS_REQUIRE(out, "enc_path_taken: null argument");
+  *out = enc_taken(backward);
+  return PS_OK;
+}
+
+int enc_layers_forward(const EncCall& c, const EncFwdOpts& o) {
+  const PsTemDesc& D = c.D; const PsTemTensors& P = c.P; float* ws = c.ws; const Ws& w = c.w; hipStream_t st = c.st;
   const int d = D.d, S = w.S, NL = D.n_layers;
-  const EncPlan pl = enc_plan(D, P, ws, w, o.rows_listed, valid);
+  const EncPlan& pl = c.plan;
   enc_taken_clear(0, NL);
   PsEncPath& tk = enc_taken(0);
   for (int i = 0; i < NL; ++i) {
@@ -308,13 +349,12 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       TRY(launch_ln_fwd(a, st));
     }
     const float* xn = ws + l.xn;
-    AttnArgs a = attn_shape(D, w, i, ui, valid);
+    AttnArgs a = attn_shape(D, w, i, c.ui, c.valid);
     a.kp = ws + l.kp; a.vp = ws + l.vp; a.qp = ws + l.qp; a.attn = ws + l.attn; a.ctx = ws + l.ctx;
     a.drop = make_drop(D, PS_SITE_ATTN(i));
     uint32_t* amask = reinterpret_cast<uint32_t*>(ws + l.amask);
-    PS_REQUIRE(!o.front == !pl.front_fused, "forward: the caller and the plan disagree about the embed launch");
     if (pl.attn[i] == ATTN_KVQ) {
-      const WSplit kvs = make_wsplit(D, P, ws, w);
+      const WSplit& kvs = c.x3;
       KvqArgs q;
       memset(&q, 0, sizeof(q));
       if (o.split_bwd_left) q.split = kvs;           // the backward-only streams, left out of the embed launch (encode_forward)
@@ -324,7 +364,7 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
       if (pl.front_fused) {                          // ... and the embed launch's work (its caller did not launch it)
         q.wkv[0] = Lp.wk; q.wkv[1] = Lp.wv;
         TRY(launch_front_attn_fwd(q, *o.front, st));
-        g_front_taken = 1;
+        g_taken.front = 1;
       } else TRY(launch_kvq_attn_fwd(q, st));
       tk.attn[i] = ATTN_KVQ; tk.rowlist = 1;         // (its workgroups project their sequence's valid positions only)
     } else {   // K, V, Q projections (neural.py:192-197), Q pre-divided by sqrt(dh) (:206)
@@ -354,11 +394,11 @@ int enc_layers_forward(const PsTemDesc& D, const PsTemTensors& P, const int64_t*
     }
     const bool fuse = pl.fwd_fuse_last && i == NL - 1;
     PS_REQUIRE(!o.fold_sc || fuse || i != NL - 1, "forward: folded scoring without the fused last layer");   // (earlier layers: never fused)
-    TRY(enc_tail_forward(D, P, ws, w, i, xin, fuse, fuse ? o.fold_sc : nullptr, st));
+    TRY(enc_tail_forward(c, c.x3, i, xin, fuse, fuse ? o.fold_sc : nullptr));
     if (fuse) { tk.fwd_fuse_last = 1; tk.fold_score = o.fold_sc ? 1 : 0; }
   }
   if (pl.fwd_fuse_last) return PS_OK;
-  return enc_final_ln_forward(D, P, ws, w, st);
+  return enc_final_ln_forward(c);
 }
 
 // park the {dgamma, dbeta, colsum} column sums of one LN backward (see ColFoldList) when the caller collects them
@@ -373,43 +413,9 @@ static void park_colsums(LnBwdArgs& a, float* ws, const Ws& w, ColFoldList* fold
   a.partial = park(fold, ws + w.lnpart + (size_t)fold->n * w.lnrows * 3 * a.d, ln_bwd_blocks(a.rows), a.d, a.dgamma, a.dbeta, a.colsum);
 }
 
-static int& fuse_bwd_min_slot() { static int v = ps_env_int("PS_FUSE_BWD_MIN", 1024); return v; }
-extern "C" int ps_set_fuse_bwd_min(int rows) { return std::exchange(fuse_bwd_min_slot(), rows); }
-
-// The item rows' gradient scatter (g_product_emb[idx(b, j)] += ds * enc[(b, j)]) rides in the fused per-replica backward, which
-// holds ds and idx already, and the score backward's launch shrinks to its word tasks (MlpBwdArgs::g_product_emb,
-// ScoreArgs::items_elsewhere), which then are the main stream's last launch instead of the side stream's first (see
-// bwd_fused_last).  PS_ITEM_SCATTER_FUSED=0: the score backward's own item workgroups, on the side stream, as before.
-// Deterministic mode never takes it (its sole-owner scatter walks the item tasks in order).
-static int& item_scatter_fused_slot() { static int v = ps_env_int("PS_ITEM_SCATTER_FUSED", 1); return v; }
-extern "C" int ps_set_item_scatter_fused(int on) { return std::exchange(item_scatter_fused_slot(), on); }
-// What the last forward [0] / backward [1] launched (encoder.h, enc_taken); item_scatter: the fused kernel scattered the item rows
-static PsEncPath g_taken[2];
-PsEncPath& enc_taken(int backward) { return g_taken[backward ? 1 : 0]; }
-void enc_taken_clear(int backward, int n_layers) {
-  PsEncPath& t = enc_taken(backward);
-  memset(&t, 0, sizeof(t));
-  if (!backward) g_front_taken = 0;
-  t.n_layers = n_layers;
-}
-extern "C" int ps_item_scatter_fused_taken(void) { return g_taken[1].item_scatter; }
-void enc_record_backward(const EncBwdOut& out) { g_taken[1].item_scatter = out.item_scatter_taken ? 1 : 0; }
-extern "C" int ps_enc_path_taken(int32_t backward, PsEncPath* out) {
-  PS_REQUIRE(out, "enc_path_taken: null argument");
-  *out = enc_taken(backward);
-  return PS_OK;
-}
-
-// The switches are read once, here; the setters' slots (ps_set_fuse_bwd_min, ps_set_item_scatter_fused, ps_set_deterministic)
-// on every call.
-EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, bool rows_listed, const float* valid) {
-  static const bool rows_on = ps_env_int("PS_NO_ROWLIST", 0) == 0;
-  static const bool bwd_fuse_on = ps_env_int("PS_NO_FUSE_BWD", 0) == 0;
-  static const bool dx_fused_on = ps_env_int("PS_KVDX_FUSED", 1) != 0;
-  static const bool wgrad_early = ps_diag_int("PS_WGRAD_LATE", 0) == 0;
-  static const int wg3_side = ps_diag_int("PS_WG3_SIDE", -1);
-  static const bool wg3_main_on = wg3_side >= 0 ? wg3_side == 0 : fork_by_kernel();
-  static const bool wg3_last = ps_diag_int("PS_WG3_LAST", 1) != 0;
+// `kvs`: make_wsplit's answer for the call (fwd_kv / bwd_kv: one-layer encoders only)
+static EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, const Ws& w, const WSplit& kvs, bool rows_listed, const float* valid) {
+  const EncSwitches& sw = enc_switches();
   EncPlan pl;
   memset(&pl, 0, sizeof(pl));
   const int NL = D.n_layers, d = D.d, S = w.S;
@@ -423,15 +429,14 @@ EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws&
   const LayerWs& ll = w.layer[NL - 1];
   const bool sq1 = pl.attn[0] != ATTN_GENERIC, wf = pl.attn[0] == ATTN_WF, w1 = wf || pl.attn[0] == ATTN_W1;
   const bool qall = l0.Sq == S;
-  const WSplit kvs = make_wsplit(D, P, ws, w);           // (fwd_kv / bwd_kv: one-layer encoders only)
-  pl.rowlist = rows_on && rows_listed && NL == 1 && w.qpos == 0 && w.vrows != 0 && l0.n_in == D.B && sq1;
+  pl.rowlist = sw.rows_on && rows_listed && NL == 1 && w.qpos == 0 && w.vrows != 0 && l0.n_in == D.B && sq1;
   // One layer, replicas, d = 128: projections + attention of the one consumed position in ONE launch, a workgroup per
   // sequence (kvq_attn_fwd_kernel): the K / V weight fragments were re-split by the embed launch in front (WSplit::fwd_kv)
   // (the streams must exist either way: ps_set_front_fused can restore that launch from one call to the next)
   if (NL == 1 && kvs.on && kvs.fwd_kv && ps_fusion_enabled() && pl.rowlist && wf && kvq_attn_fits(a0) && l0.amask) pl.attn[0] = ATTN_KVQ;
   // ... and the embed launch in front of it as well (front_attn_fwd_kernel): FS query encoder (projected in the launch), positional
   // rows, at most PS_FRONT_MAX_Q query words; the AVG encoder and longer queries keep the two launches
-  pl.front_fused = pl.attn[0] == ATTN_KVQ && front_fused_slot() != 0 && D.query_encoder == PS_QENC_FS && D.use_pos_emb &&
+  pl.front_fused = pl.attn[0] == ATTN_KVQ && sw.front_fused != 0 && D.query_encoder == PS_QENC_FS && D.use_pos_emb &&
                    D.Q >= 1 && D.Q <= PS_FRONT_MAX_Q && P.fs_w && P.fs_b && P.pe && kvs.bwd_kv;
   const bool last_fusable = ps_fusion_enabled() && ll.Sq == 1 && mlp_fused_serves(d, D.F) && w.wsplit;
   pl.fwd_fuse_last = last_fusable && P.final_ln_g && P.final_ln_b;
@@ -441,11 +446,11 @@ EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws&
   EncPlan::Bwd& b = pl.bwd;
   // The last layer's whole per-replica backward (final LN, FFN, FF LN, Wo) as one kernel (mlp_fused.hip) when the
   // forward took the fused form too; needs parked column sums (fold) and one parked row per workgroup (Ws::lnrows of them).
-  b.fuse_last = last_fusable && bwd_fuse_on && ll.M2 == w.Mf && w.Mf >= fuse_bwd_min_slot() && mlp_bwd_fused_blocks(w.Mf) <= w.lnrows;
-  b.item_scatter = b.fuse_last && item_scatter_fused_slot() != 0 && !ps_deterministic();
-  b.wg3_main = b.fuse_last && wg3_main_on && ll.n_in * S <= 2 * ll.M2;   // (review transformer: 78k K/V rows vs 1.5k replica rows -> side)
-  b.wg3_last = b.wg3_main && wg3_last && NL == 1;
-  b.wgrad_early = wgrad_early;
+  b.fuse_last = last_fusable && sw.bwd_fuse_on && ll.M2 == w.Mf && w.Mf >= sw.fuse_bwd_min && mlp_bwd_fused_blocks(w.Mf) <= w.lnrows;
+  b.item_scatter = b.fuse_last && sw.item_scatter_fused != 0 && !ps_deterministic();
+  b.wg3_main = b.fuse_last && sw.wg3_main_on && ll.n_in * S <= 2 * ll.M2;   // (review transformer: 78k K/V rows vs 1.5k replica rows -> side)
+  b.wg3_last = b.wg3_main && sw.wg3_last && NL == 1;
+  b.wgrad_early = sw.wgrad_early;
   // first layer, one query row per sequence, d == 128: dQ.Wq rides in the attention backward's tail (two partial
   // rows per sequence in the free d ln1 buffer) instead of a [n_in,128]x[128,128] GEMM launch of its own
   b.q_folded = sq1 && !qall && ps_fusion_enabled() &&
@@ -457,7 +462,7 @@ EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws&
   // ... and, one-layer encoder with replicas: so does the K / V input gradient itself (AttnArgs::kvb_stream) — no dX GEMM launch
   // on the dependent chain; the embed scatter adds the two head groups' partial rows (EmbedBwdArgs::dx2)
   // (FS query encoder only: its fused backward reads d query_emb as the two partials; the AVG branch copies one row of dx)
-  b.dx_fused = dx_fused_on && wf && b.q_folded && b.listed && d == 128 && kvs.on && kvs.bwd_kv && !ps_deterministic() &&
+  b.dx_fused = sw.dx_fused_on && wf && b.q_folded && b.listed && d == 128 && kvs.on && kvs.bwd_kv && !ps_deterministic() &&
                attn_bwd_wf_two_partials(a0) && D.query_encoder == PS_QENC_FS;
   // round 4: where dQ.Wq is NOT folded (d != 128: the C5 shard) the replicas' fan-in is summed by a launch of its own
   // (launch_fanin_sum) so that the dX product can still run over the row list: 133 -> ~50 us at C5
@@ -465,10 +470,15 @@ EncPlan enc_plan(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws&
   return pl;
 }
 
-// What the three sequences of the encoder backward share
-struct EncBwd {
-  const PsTemDesc& D; const PsTemTensors& P; const PsTemTensors& G; float* ws; const Ws& w; hipStream_t st;
-  const EncPlan& pl; const EncBwdIn& in; EncBwdOut& out;
+EncCall enc_call(const EncBase& b, const int64_t* ui, const float* valid, bool rows_listed) {
+  EncCall c = {b, ui, valid, rows_listed, {}, make_wsplit(b.D, b.P, b.ws, b.w)};
+  c.plan = enc_plan(b.D, b.P, b.w, c.x3, rows_listed, valid);
+  return c;
+}
+
+// What the three sequences of the encoder backward share: the call, the gradients, the caller's options and what it gets back
+struct EncBwd : EncCall {
+  const PsTemTensors& G; const EncBwdIn& in; EncBwdOut& out;
   bool drop() const { return D.training && D.dropout > 0.f; }
   const float* do2() const { return drop() ? ws + w.do2 : ws + w.dy2; }     // d y2 behind the FF2 dropout
   const float* dout() const { return drop() ? ws + w.do_ : ws + w.dy1; }    // d y1 behind the context dropout
@@ -499,12 +509,12 @@ static int bwd_fused_last(const EncBwd& c, const ScoreArgs* score) {
     const ScoreArgs& sa = *score;
     m.item_scores = sa.item_scores; m.target = sa.target; m.neg_items = sa.neg_items; m.product_emb = sa.product_emb;
     m.B = sa.B; m.K = sa.K; m.pos_weight = sa.pos_weight; m.P = sa.P; m.scale = sa.scale; m.scale_dev = sa.scale_dev;
-    if (c.pl.bwd.item_scatter && c.in.caller_flushes_tail && sa.part == 0 && sa.enc && sa.g_product_emb) {
+    if (c.plan.bwd.item_scatter && c.in.caller_flushes_tail && sa.part == 0 && sa.enc && sa.g_product_emb) {
       m.enc = sa.enc; m.g_product_emb = sa.g_product_emb;
       m.g_product_bias = sa.bias_product ? sa.g_product_bias : nullptr;
     }
   }
-  m.x3 = make_wsplit(D, c.P, ws, w);                 // the fragment streams the forward's embed launch left in the workspace
+  m.x3 = c.x3;                                       // the fragment streams the forward's embed launch left in the workspace
   m.do2 = const_cast<float*>(c.do2()); m.da1 = ws + w.da1; m.dy1 = ws + w.dy1;
   m.dout = const_cast<float*>(c.dout()); m.dctx = ws + w.dctx;
   const int nwg = mlp_bwd_fused_blocks(M2);
@@ -567,7 +577,7 @@ static int bwd_ffn(const EncBwd& c, int i) {
   // fork 1: the two big weight gradients (W2, W1) start as soon as d a1 exists, under the LN backward, the Wo dX
   // GEMM and the attention backward.  (Forked one GEMM later, behind d ctx, the side stream's 112 us of weight
   // gradients ended 13 us after the main chain and the step paid a late join on top.)
-  if (c.pl.bwd.wgrad_early) {
+  if (c.plan.bwd.wgrad_early) {
     TRY(side_fork(st));
     TRY(side_run(wg, 1, st));
     TRY(side_run(wg1, 1, st));
@@ -585,7 +595,7 @@ static int bwd_ffn(const EncBwd& c, int i) {
   TRY(launch_ln_bwd(n, st));
   GemmProblem pc = gp(c.dout(), d, 0, Lp.wo, d, 1, ws + w.dctx, d, M2, d, d);    // d ctx = do . Wo
   TRY(run1(pc, st));
-  if (!c.pl.bwd.wgrad_early) {
+  if (!c.plan.bwd.wgrad_early) {
     GemmProblem wgo[1] = {c.wgrad_wo(i)};
     TRY(side_fork(st));                         // fork 1 (late form): W2, W1, Wo weight gradients under the attention backward
     TRY(side_run(wg, 1, st));
@@ -597,9 +607,9 @@ static int bwd_ffn(const EncBwd& c, int i) {
 
 // Layer i's attention backward, the K / V / Q weight gradients and the input gradient d xn = dK.Wk + dV.Wv (+ dQ.Wq).
 // `fused`: bwd_fused_last ran in front (the side stream holds W2 / W1 / Wo), not bwd_ffn.
-static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, const float* valid) {
+static int bwd_attention(const EncBwd& c, int i, bool fused) {
   const PsTemDesc& D = c.D; const Ws& w = c.w; float* ws = c.ws; hipStream_t st = c.st;
-  const EncPlan::Bwd& pb = c.pl.bwd;
+  const EncPlan::Bwd& pb = c.plan.bwd;
   const int d = D.d, S = w.S;
   const LayerWs& l = w.layer[i];
   const PsLayerTensors& Lp = c.P.layer[i];
@@ -607,7 +617,7 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
   const float* xn = ws + l.xn;
   const int ns = l.n_in * S;
   ColFoldList* fold = c.in.fold;
-  AttnArgs a = attn_shape(D, w, i, ui, valid);
+  AttnArgs a = attn_shape(D, w, i, c.ui, c.valid);
   a.kp = ws + l.kp; a.vp = ws + l.vp; a.qp = ws + l.qp; a.attn = ws + l.attn;
   a.drop = make_drop(D, PS_SITE_ATTN(i));
   a.dctx = ws + w.dctx;
@@ -617,7 +627,7 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
   a.dq = qall ? ws + w.dkv + 2 * d : ws + w.dq;
   a.lddq = qall ? 3 * d : d;
   a.dbq = Lg.bq; a.dbk = Lg.bk; a.dbv = Lg.bv;
-  const AttnForm form = c.pl.attn[i];
+  const AttnForm form = c.plan.attn[i];
   const bool wf = form == ATTN_WF || form == ATTN_KVQ;   // one wave per (sequence, four heads), replicas inside
   const bool w1 = wf || form == ATTN_W1;                 // one wave per sequence (no replicas)
   if (form != ATTN_GENERIC && fold && fold->n < PS_MAX_COLFOLD)   // bias gradients: one parked row per sequence instead of n_in same-address atomics per column
@@ -626,7 +636,7 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
   const bool q_folded = i == 0 && pb.q_folded, listed = pb.listed, presum = pb.presum, dx_fused = pb.dx_fused;
   PsEncPath& tk = enc_taken(1);
   if (q_folded) { a.wq = Lp.wq; a.dxq_part = ws + w.dln1; a.fanin_src = ws + w.dy1; tk.q_folded = 1; }
-  if (dx_fused) { a.kvb_stream = make_wsplit(D, c.P, ws, w).bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; tk.dx_fused = 1; }
+  if (dx_fused) { a.kvb_stream = c.x3.bwd_kv; a.dxp[0] = ws + w.dx; a.dxp[1] = ws + w.dxn; tk.dx_fused = 1; }
   c.out.dx_two_partials = dx_fused;
   const bool pads_unread = listed && (q_folded || l.fan == 1 || presum);
   if (wf) {
@@ -717,15 +727,14 @@ static int bwd_attention(const EncBwd& c, int i, bool fused, const int64_t* ui, 
   return PS_OK;
 }
 
-int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTensors& G, const int64_t* ui,
-                        const float* valid, float* ws, const Ws& w, hipStream_t st, const EncBwdIn& in, EncBwdOut& out) {
+int enc_layers_backward(const EncCall& call, const PsTemTensors& G, const EncBwdIn& in, EncBwdOut& out) {
+  const PsTemDesc& D = call.D; const PsTemTensors& P = call.P; float* ws = call.ws; const Ws& w = call.w; hipStream_t st = call.st;
   const int B = D.B, d = D.d, S = w.S, NL = D.n_layers;
   PS_REQUIRE(G.final_ln_g && G.final_ln_b, "backward: null final LayerNorm gradient");
-  const EncPlan pl = enc_plan(D, P, ws, w, in.rows_listed, valid);
   out = EncBwdOut();
   enc_taken_clear(1, NL);
-  const EncBwd c = {D, P, G, ws, w, st, pl, in, out};
-  const bool fuse_last = pl.bwd.fuse_last;
+  const EncBwd c = {call, G, in, out};
+  const bool fuse_last = c.plan.bwd.fuse_last;
   side_set_light((int64_t)B * S * d <= ((int64_t)2 << 20));   // C2: 1.03 M elements of x; review transformer 10 M; C5 5.5 M
   const ScoreArgs* score_fused = fuse_last && w.R > 1 ? in.score_on_side : nullptr;
   if (in.score_on_side && !score_fused) {
@@ -772,7 +781,7 @@ int enc_layers_backward(const PsTemDesc& D, const PsTemTensors& P, const PsTemTe
     const bool fused = fuse_last && i == NL - 1;
     if (fused) TRY(bwd_fused_last(c, score_fused));
     else TRY(bwd_ffn(c, i));
-    TRY(bwd_attention(c, i, fused, ui, valid));
+    TRY(bwd_attention(c, i, fused));
     if (i != 0) {   // pre-LayerNorm backward -> grad wrt the previous layer's output
       TRY(side_join(st));   // the next layer reuses the scratch buffers the side-stream GEMMs read
       PS_REQUIRE(Lg.ln_g && Lg.ln_b, "backward: layer %d null pre-LN gradient", i);

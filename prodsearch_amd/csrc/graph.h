@@ -133,3 +133,30 @@ inline int ps_graph_patch(PsGraphEntry* e, int p, void** kernel_params) {
 inline int ps_graph_launch(PsGraphEntry* e, hipStream_t st) {
   return hipGraphLaunch(e->exec, st) == hipSuccess ? PS_OK : 1;
 }
+
+// One call of an entry point through its table entry `e` (null — graphs off, or the table is full —: eager).  `body(stream)`
+// issues the entry's launch sequence on that stream.  First sight: eager.  Second: captured on the private stream, then launched;
+// whatever fails to capture marks the entry bad and runs eagerly on the caller's stream.  From then on: `patch` (kernels taking one
+// by-value argument struct each, n_patch <= PS_GRAPH_PATCH) refreshed from their `arg`, and a replay.
+struct PsGraphPatch { const void* func; void* arg; };
+template <class Body>
+inline int ps_graph_step(PsGraphEntry* e, hipStream_t st, const char* entry, const PsGraphPatch* patch, int n_patch, Body&& body) {
+  if (e && e->state == 2) {
+    int rc = PS_OK;
+    for (int p = 0; p < n_patch && !rc; ++p) { void* arg[1] = {patch[p].arg}; rc = ps_graph_patch(e, p, arg); }
+    if (!rc) rc = ps_graph_launch(e, st);
+    if (rc) ps_set_error("%s: graph replay failed", entry);
+    return rc;
+  }
+  hipStream_t cap = (e && e->state == 1) ? ps_graph_begin() : nullptr;
+  if (!cap) {
+    if (e && e->state == 0) e->state = 1;
+    return body(st);
+  }
+  const int rc = body(cap);
+  const void* funcs[PS_GRAPH_PATCH];
+  for (int p = 0; p < n_patch; ++p) funcs[p] = patch[p].func;
+  if (ps_graph_end(cap, e, funcs, n_patch) == PS_OK && rc == PS_OK) return ps_graph_launch(e, st);
+  e->state = -1;
+  return body(st);
+}

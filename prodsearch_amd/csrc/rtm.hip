@@ -260,11 +260,10 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
   PS_REQUIRE(!e.fs || (P.fs_w && P.fs_b), "rtm: null FS encoder weights");
   const bool fs_fused = e.fs && ps_fusion_enabled() && d <= 128;
   if (fs_fused) { e.fs_w = P.fs_w; e.fs_b = P.fs_b; }
-  const bool listed = rtm_rows_listed(r, w);
   PsTemTensors T;
   to_tem_tensors(P, T);
-  const EncPlan plan = enc_plan(E, T, ws + r.enc_base, w, listed, ws + r.valid);   // what enc_layers_forward will decide
-  e.split = make_wsplit(E, T, ws + r.enc_base, w);      // the fused kernels' bf16x3 weight planes ride in this launch
+  const EncCall c = enc_call({E, T, ws + r.enc_base, w, st}, nullptr, ws + r.valid, rtm_rows_listed(r, w));
+  e.split = c.x3;                                       // the fused kernels' bf16x3 weight planes ride in this launch
   // the backward's inverted index (rtm_counts_in_forward): its counters are cleared by this launch, filled by the next
   k.count_fwd = !eval && rtm_bwd_plan(D, r, k.det != 0).index == PS_RTM_INDEX_FWD_COUNTS;      // (none with a frozen word table)
   if (k.count_fwd) { e.zero_i32 = k.wcnt; e.zero_n = (int)D.vocab_size + 1; }
@@ -276,7 +275,7 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
     TRY(run1(p, st));
   }
   PS_REQUIRE(!D.use_pos_emb || P.pe, "rtm: null positional table");
-  TRY(rtm_embed_fwd(D, k, ws, r, eval, plan.rowlist, st));
+  TRY(rtm_embed_fwd(D, k, ws, r, eval, c.plan.rowlist, st));
   if (k.raw) {   // fs review encoder: y = tanh(f_W . raw + b) for every review slot, then the rest of x
     PS_REQUIRE(P.rev_fs_w && P.rev_fs_b, "rtm: null review-encoder f_W");
     GemmProblem p = gp(ws + r.raw, d, 0, P.rev_fs_w, d, 0, ws + r.yfs, d, r.Bseq * D.R, d, d);
@@ -284,10 +283,8 @@ static int rtm_encode(const PsRtmDesc& D, const PsRtmTensors& P, const PsRtmBatc
     TRY(run1(p, st));
     TRY(rtm_fs_finish(k, r, st));
   }
-  if (listed) TRY(rtm_rowlist(k, r, st));
-  EncFwdOpts o;
-  o.rows_listed = listed;
-  return enc_layers_forward(E, T, nullptr, ws + r.valid, ws + r.enc_base, w, st, o);
+  if (c.rows_listed) TRY(rtm_rowlist(k, r, st));
+  return enc_layers_forward(c, EncFwdOpts());
 }
 
 extern "C" int ps_rtm_forward(const PsRtmDesc* desc, const PsRtmTensors* params, const PsRtmBatch* batch, float* ws,
@@ -398,8 +395,8 @@ static int rtm_backward_impl(const PsRtmDesc* desc, const PsRtmTensors* params, 
   }
   if (pl.slot_rows) k.gs = ws + r.enc_base + w.dx;     // (det + pv encoder: the review rows' gradients are parked in place, scattered by the embed backward)
   EncBwdIn in;
-  in.fold = &fold; in.rows_listed = rtm_rows_listed(r, w);
-  TRY(enc_layers_backward(E, T, TG, nullptr, ws + r.valid, ws + r.enc_base, w, st, in, out));
+  in.fold = &fold;
+  TRY(enc_layers_backward(enc_call({E, T, ws + r.enc_base, w, st}, nullptr, ws + r.valid, rtm_rows_listed(r, w)), TG, in, out));
   PS_REQUIRE(!out.dx_two_partials, "rtm backward: the encoder left d x as two partials, which nothing here adds");
   // ---- fs: through the review projection: d pre = dx * tanh', bias gradient, weight gradient, d raw = d pre . f_W
   if (D.review_encoder == PS_RENC_FS) {

@@ -617,6 +617,7 @@ static int rr_launch_walk(const RrK& k, int epl, hipStream_t st) {
 struct RrCall {
   PsTemDesc E;
   PsTemTensors Tt;                                   // the tail's view: no K / V streams in the weight split
+  WSplit x3;                                         // ... (all zero without the fused tail)
   RrK k;
   int epl;
 };
@@ -642,6 +643,7 @@ static int rr_entry_side(const PsRtmDesc& D, const PsRtmRankShape& Sh, const PsR
   if (fs_fused) { e.fs_w = P.fs_w; e.fs_b = P.fs_b; }
   if (r.fuse) { e.split = make_wsplit(E, Tt, ws, r.w); e.split_fwd_only = 1; }
   PS_REQUIRE(!r.fuse || e.split.on, "rtm rank_all: the fused tail's weight split is missing");
+  c.x3 = e.split;
   TRY(launch_embed_fwd(e, st));
   if (e.fs && !fs_fused) {
     GemmProblem p = gp(ws + r.qmean, d, 0, P.fs_w, d, 0, ws + r.qemb, d, B, d, d);
@@ -724,8 +726,9 @@ static int rr_run(const PsRtmDesc& D, const PsRtmRankShape& Sh, const PsRtmTenso
     k.i0 = (int)c0;
     k.nv = (int)(c0 + r.tile <= N ? r.tile : N - c0);
     TRY(rr_launch_walk(k, c.epl, st));
-    TRY(enc_tail_forward(c.E, c.Tt, ws, r.w, 0, ws + r.x0, r.fuse, nullptr, st));
-    if (!r.fuse) TRY(enc_final_ln_forward(c.E, c.Tt, ws, r.w, st));
+    const EncBase eb = {c.E, c.Tt, ws, r.w, st};
+    TRY(enc_tail_forward(eb, c.x3, 0, ws + r.x0, r.fuse, nullptr));
+    if (!r.fuse) TRY(enc_final_ln_forward(eb));
     hipLaunchKernelGGL(rr_head_kernel, dim3(ps_cdiv((int64_t)B * r.tile, 4)), dim3(256), 0, st, ws + r.w.enc, P.wo_w, P.wo_b, src.candi, B,
                        r.tile, k.nv, d, k.i0, k.C, k.P, k.ldS, S);
     PS_LAUNCH_CHECK();

@@ -22,8 +22,29 @@ struct SamplerArgs { const float* prob; const int32_t* alias; int64_t* items; in
 // (B^2 L / 2 index reads in total): fine up to a few thousand sequences, dense products beyond
 static bool rows_list_ok(const PsTemDesc& D) { return D.L <= 64 && (int64_t)D.B * D.B * D.L <= ((int64_t)64 << 20); }
 
-static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
-                          hipStream_t st, const SamplerArgs* samp = nullptr, const ScoreArgs* fold_sc = nullptr) {
+// ---- one call object per entry point: the descriptor as the entry's mode reads it, the workspace layout, the stream, whether the
+// valid-row list is built; `rc`: make_ws's answer (bad descriptor), to be checked right behind the constructor.  base / enc: the
+// encoder's views of the call (encoder.h), made where the entry has the tensors and the workspace.
+enum TemMode {
+  TEM_TRAIN,                // a training-mode forward / backward: no candidates (C = 0)
+  TEM_EVAL,                 // ps_tem_score / ps_tem_encode: C candidates, no dropout drawn
+  TEM_DESCRIBED             // as the descriptor says (ps_tem_plan): C > 0 describes an eval call, C == 0 a training-mode one
+};
+struct TemCall {
+  PsTemDesc D; Ws w; hipStream_t st; bool listed; int rc;
+  TemCall(const PsTemDesc* desc, TemMode mode, ps_stream_t stream) : D(*desc), st((hipStream_t)stream) {
+    if (mode == TEM_TRAIN) D.C = 0;
+    if (mode == TEM_EVAL || (mode == TEM_DESCRIBED && D.C > 0)) D.training = 0;
+    rc = make_ws(D, w);
+    listed = rows_list_ok(D);
+  }
+  TemCall(const TemCall&) = delete;             // (the views below point into it)
+  EncBase base(const PsTemTensors& P, float* ws) const { return {D, P, ws, w, st}; }
+  EncCall enc(const PsTemTensors& P, float* ws, const int64_t* ui, hipStream_t on) const { return enc_call({D, P, ws, w, on}, ui, nullptr, listed); }
+};
+
+static int encode_forward(const EncCall& c, const PsTemBatch& Bt, const SamplerArgs* samp = nullptr, const ScoreArgs* fold_sc = nullptr) {
+  const PsTemDesc& D = c.D; const PsTemTensors& P = c.P; float* ws = c.ws; const Ws& w = c.w; hipStream_t st = c.st;
   const bool tem = D.model == PS_MODEL_TEM;
   const int B = D.B, d = D.d, S = w.S;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
@@ -39,7 +60,7 @@ static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTem
   e.qmean_d = ws + w.qmean; e.query_emb = ws + w.query_emb; e.x = ws + w.x;
   PS_REQUIRE(e.qw && ((!tem && !ps_model_attn(D.model)) || e.ui), "forward: null batch indices");
   PS_REQUIRE(!tem || !D.use_pos_emb || P.pe, "forward: null positional table");
-  if (tem && rows_list_ok(D)) { e.vrows = reinterpret_cast<int32_t*>(ws + w.vrows); e.vcount = reinterpret_cast<int32_t*>(ws + w.vcount); }
+  if (tem && c.rows_listed) { e.vrows = reinterpret_cast<int32_t*>(ws + w.vrows); e.vcount = reinterpret_cast<int32_t*>(ws + w.vcount); }
   const float* wp_w[PS_WPLANES_MAX]; int wp_r[PS_WPLANES_MAX], wp_c[PS_WPLANES_MAX];
   const int wp_n = wplane_list(D, P, w, wp_w, wp_r, wp_c);
   WPlaneScope wplanes(st, wp_w, wp_r, wp_c, wp_n);             // the big linears multiply against pre-split weight planes (gemm_kernels.hip)
@@ -54,17 +75,16 @@ static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTem
   const bool fs_fused = e.fs && ps_fusion_enabled() && d <= 128;
   if (fs_fused) { e.fs_w = P.fs_w; e.fs_b = P.fs_b; }
   if (fold_sc) { e.fold_words = 1; e.sc = *fold_sc; }
-  e.split = make_wsplit(D, P, ws, w);
+  e.split = c.x3;
   EncFwdOpts o;
-  o.rows_listed = rows_list_ok(D); o.fold_sc = fold_sc;
-  const EncPlan pl = enc_plan(D, P, ws, w, o.rows_listed, nullptr);
-  if (tem && pl.front_fused) {                   // one launch embeds, projects and attends: layer 0's (enc_layers_forward)
+  o.fold_sc = fold_sc;
+  if (tem && c.plan.front_fused) {               // one launch embeds, projects and attends: layer 0's (enc_layers_forward)
     PS_REQUIRE(fs_fused && e.vrows, "forward: the fused front end needs the FS projection and the row list");
     o.front = &e;
-    return enc_layers_forward(D, P, Bt.u_item_idxs, nullptr, ws, w, st, o);
+    return enc_layers_forward(c, o);
   }
   // the fused projection + attention launch re-splits the backward's streams
-  o.split_bwd_left = e.split.on && D.training && pl.attn[0] == ATTN_KVQ;
+  o.split_bwd_left = e.split.on && D.training && c.plan.attn[0] == ATTN_KVQ;
   e.split_fwd_only = o.split_bwd_left ? 1 : 0;
   TRY(launch_embed_fwd(e, st));
   if (e.fs && !fs_fused) {   // FSEncoder: tanh(f_W . mean + b)  (text_encoder.py:39); also writes row 0 of x (+pe[0])
@@ -73,16 +93,13 @@ static int encode_forward(const PsTemDesc& D, const PsTemTensors& P, const PsTem
     if (tem) { p.out2 = ws + w.x; p.ld2 = S * d; p.add2 = D.use_pos_emb ? P.pe : nullptr; }
     TRY(run1(p, st));
   }
-  if (ps_model_attn(D.model)) return ae_forward(D, P, Bt.u_item_idxs, ws, w, st);
+  if (ps_model_attn(D.model)) return ae_forward(c);
   if (!tem) return PS_OK;
-  return enc_layers_forward(D, P, Bt.u_item_idxs, nullptr, ws, w, st, o);
+  return enc_layers_forward(c, o);
 }
 
-// Folded scoring (EncPlan::fold_score) — not on a capturing stream: graph replay patches the loss kernel's arguments (unfolded form)
-static bool can_fold_score(const PsTemDesc& D, const PsTemTensors& P, float* ws, const Ws& w, hipStream_t st) {
-  return enc_plan(D, P, ws, w, rows_list_ok(D), nullptr).fold_score && !stream_capturing(st);
-}
-static void fold_finish(const PsTemDesc& D, float* ws, const Ws& w, ScoreArgs& s, const SamplerArgs* samp) {
+static void fold_finish(const EncBase& c, ScoreArgs& s, const SamplerArgs* samp) {
+  const PsTemDesc& D = c.D; float* ws = c.ws; const Ws& w = c.w;
   s.word_blk = ws + w.word_blk; s.item_blk = ws + w.item_blk; s.ticket = reinterpret_cast<uint32_t*>(ws + w.ticket);
   s.word_nblk = ps_cdiv((int64_t)D.B * D.W * (D.K + 1), PS_WORD_TASKS_PER_WG);
   if (samp) {
@@ -91,8 +108,8 @@ static void fold_finish(const PsTemDesc& D, float* ws, const Ws& w, ScoreArgs& s
   }
 }
 
-static void fill_score(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bt, float* ws, const Ws& w,
-                       ScoreArgs& s) {
+static void fill_score(const EncBase& c, const PsTemBatch& Bt, ScoreArgs& s) {
+  const PsTemDesc& D = c.D; const PsTemTensors& P = c.P; float* ws = c.ws; const Ws& w = c.w;
   memset(&s, 0, sizeof(s));
   s.B = D.B; s.K = D.K; s.W = D.W; s.C = 0; s.R = w.R; s.d = D.d;
   s.P = D.product_size; s.V = D.vocab_size;
@@ -106,28 +123,33 @@ static void fill_score(const PsTemDesc& D, const PsTemTensors& P, const PsTemBat
   score_finish(s);
 }
 
+// The training forward of ps_tem_forward, ps_tem_forward_sampled and ps_tem_forward_step: [the staging prologue,] embed + encode,
+// score, loss.  Folded scoring (EncPlan::fold_score: no gather+score / loss launches, see ScoreArgs, folded form) where the caller
+// allows it and the stream is not capturing: graph replay patches the loss kernel's arguments (unfolded form).
+static int tem_forward(const EncCall& c, const PsTemBatch& Bt, const SamplerArgs* samp, float* loss3, float* loss_acc, bool may_fold,
+                       const StageArgs* stage) {
+  if (stage) TRY(launch_stage(*stage, c.st));
+  ScoreArgs s;
+  fill_score(c, Bt, s);
+  s.loss3 = loss3; s.loss_acc = loss_acc;
+  if (may_fold && c.plan.fold_score && !stream_capturing(c.st)) {
+    fold_finish(c, s, samp);
+    return encode_forward(c, Bt, samp, &s);
+  }
+  TRY(encode_forward(c, Bt, samp));
+  TRY(launch_score_fwd(s, c.st));
+  return launch_loss(s, c.st);
+}
+
 extern "C" int ps_tem_forward(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                               float* workspace, float* loss3, float* loss_acc, ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && workspace && loss3, "forward: null argument");
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
-  PS_REQUIRE(batch->target_prod_idxs && batch->neg_item_idxs && (D.W == 0 || (batch->pos_iword_idxs &&
+  const TemCall t(desc, TEM_TRAIN, stream);
+  TRY(t.rc);
+  PS_REQUIRE(batch->target_prod_idxs && batch->neg_item_idxs && (t.D.W == 0 || (batch->pos_iword_idxs &&
              batch->neg_word_idxs)), "forward: null batch tensors");
-  PS_REQUIRE(params->word_bias && (!D.bias_product || params->product_bias), "forward: null bias tensors");
-  ScoreArgs s;
-  fill_score(D, *params, *batch, workspace, w, s);
-  s.loss3 = loss3; s.loss_acc = loss_acc;
-  if (can_fold_score(D, *params, workspace, w, st)) {             // no gather+score / loss launches: see ScoreArgs, folded form
-    fold_finish(D, workspace, w, s, nullptr);
-    return encode_forward(D, *params, *batch, workspace, w, st, nullptr, &s);
-  }
-  TRY(encode_forward(D, *params, *batch, workspace, w, st));
-  TRY(launch_score_fwd(s, st));
-  TRY(launch_loss(s, st));
-  return PS_OK;
+  PS_REQUIRE(params->word_bias && (!t.D.bias_product || params->product_bias), "forward: null bias tensors");
+  return tem_forward(t.enc(*params, workspace, batch->u_item_idxs, t.st), *batch, nullptr, loss3, loss_acc, true, nullptr);
 }
 
 // forward with the two negative draws folded into its first launch: neg_item_out / neg_word_out receive the draws
@@ -138,27 +160,14 @@ extern "C" int ps_tem_forward_sampled(const PsTemDesc* desc, const PsTemTensors*
                                       ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && workspace && loss3 && alias_prob && alias_idx && neg_item_out && neg_word_out,
              "forward_sampled: null argument");
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
-  PS_REQUIRE(batch->target_prod_idxs && (D.W == 0 || batch->pos_iword_idxs), "forward_sampled: null batch tensors");
-  PS_REQUIRE(params->word_bias && (!D.bias_product || params->product_bias), "forward_sampled: null bias tensors");
+  const TemCall t(desc, TEM_TRAIN, stream);
+  TRY(t.rc);
+  PS_REQUIRE(batch->target_prod_idxs && (t.D.W == 0 || batch->pos_iword_idxs), "forward_sampled: null batch tensors");
+  PS_REQUIRE(params->word_bias && (!t.D.bias_product || params->product_bias), "forward_sampled: null bias tensors");
   PsTemBatch Bt = *batch;
   Bt.neg_item_idxs = neg_item_out; Bt.neg_word_idxs = neg_word_out;
   const SamplerArgs samp = {alias_prob, alias_idx, neg_item_out, neg_word_out};
-  ScoreArgs s;
-  fill_score(D, *params, Bt, workspace, w, s);
-  s.loss3 = loss3; s.loss_acc = loss_acc;
-  if (can_fold_score(D, *params, workspace, w, st)) {
-    fold_finish(D, workspace, w, s, &samp);
-    return encode_forward(D, *params, Bt, workspace, w, st, &samp, &s);
-  }
-  TRY(encode_forward(D, *params, Bt, workspace, w, st, &samp));
-  TRY(launch_score_fwd(s, st));
-  TRY(launch_loss(s, st));
-  return PS_OK;
+  return tem_forward(t.enc(*params, workspace, Bt.u_item_idxs, t.st), Bt, &samp, loss3, loss_acc, true, nullptr);
 }
 
 // Unit-test hook (prodsearch_hip.h): the forward with the embed launch in front (ws_a) and inside the projection + attention
@@ -170,11 +179,10 @@ extern "C" int ps_front_fused_test(const PsTemDesc* desc, const PsTemTensors* pa
                                    int64_t* neg_item_b, int64_t* neg_word_b, float* loss3_a, float* loss3_b, double* diff,
                                    int32_t* taken, ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && ws_a && ws_b && diff && taken && batch->u_item_idxs, "front_fused_test: null argument");
-  const PsTemDesc& D = *desc;
-  PS_REQUIRE(D.model == PS_MODEL_TEM && D.n_layers >= 1, "front_fused_test: an item-transformer step with encoder layers");
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
+  PS_REQUIRE(desc->model == PS_MODEL_TEM && desc->n_layers >= 1, "front_fused_test: an item-transformer step with encoder layers");
+  const TemCall t(desc, TEM_DESCRIBED, stream);   // (the layout to compare by; the two forwards build their own calls)
+  TRY(t.rc);
+  const PsTemDesc& D = t.D; const Ws& w = t.w; hipStream_t st = t.st;
   const int old = ps_set_front_fused(0);
   int rc = ps_tem_forward_sampled(desc, params, batch, alias_prob, alias_idx, neg_item_a, neg_word_a, ws_a, loss3_a, nullptr, stream);
   taken[0] = ps_front_fused_taken();
@@ -254,30 +262,25 @@ extern "C" int ps_front_fused_test(const PsTemDesc* desc, const PsTemTensors* pa
 extern "C" int ps_gather_score(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                                float* workspace, ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && workspace, "gather_score: null argument");
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
+  const TemCall t(desc, TEM_TRAIN, stream);
+  TRY(t.rc);
   ScoreArgs s;
-  fill_score(D, *params, *batch, workspace, w, s);
-  return launch_score_fwd(s, (hipStream_t)stream);
+  fill_score(t.base(*params, workspace), *batch, s);
+  return launch_score_fwd(s, t.st);
 }
 
 extern "C" int ps_tem_score(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                             float* workspace, float* scores, ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && workspace && scores, "score: null argument");
-  PsTemDesc D = *desc;
-  PS_REQUIRE(D.C > 0 && batch->candi_prod_idxs, "score: needs C > 0 candidates");
-  D.training = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
-  TRY(encode_forward(D, *params, *batch, workspace, w, st));
+  PS_REQUIRE(desc->C > 0 && batch->candi_prod_idxs, "score: needs C > 0 candidates");
+  const TemCall t(desc, TEM_EVAL, stream);
+  TRY(t.rc);
+  const EncCall c = t.enc(*params, workspace, batch->u_item_idxs, t.st);
+  TRY(encode_forward(c, *batch));
   ScoreArgs s;
-  fill_score(D, *params, *batch, workspace, w, s);
-  s.C = D.C; s.item_scores = scores; score_finish(s);
-  TRY(launch_score_fwd(s, st));
-  return PS_OK;
+  fill_score(c, *batch, s);
+  s.C = t.D.C; s.item_scores = scores; score_finish(s);
+  return launch_score_fwd(s, t.st);
 }
 
 // model.eval() sequence representation the dot-product heads consume (item_transformer.py:118-131): one encode per
@@ -285,24 +288,20 @@ extern "C" int ps_tem_score(const PsTemDesc* desc, const PsTemTensors* params, c
 extern "C" int ps_tem_encode(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                              float* workspace, float* enc_out, ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && workspace && enc_out, "encode: null argument");
-  PsTemDesc D = *desc;
-  PS_REQUIRE(D.C > 0, "encode: build the descriptor in eval mode (C >= 1)");
-  D.training = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
-  TRY(encode_forward(D, *params, *batch, workspace, w, st));
-  PS_CHECK_HIP(hipMemcpyAsync(enc_out, workspace + w.enc, sizeof(float) * (size_t)D.B * D.d, hipMemcpyDeviceToDevice, st));
+  PS_REQUIRE(desc->C > 0, "encode: build the descriptor in eval mode (C >= 1)");
+  const TemCall t(desc, TEM_EVAL, stream);
+  TRY(t.rc);
+  TRY(encode_forward(t.enc(*params, workspace, batch->u_item_idxs, t.st), *batch));
+  PS_CHECK_HIP(hipMemcpyAsync(enc_out, workspace + t.w.enc, sizeof(float) * (size_t)t.D.B * t.D.d, hipMemcpyDeviceToDevice, t.st));
   return PS_OK;
 }
 
 extern "C" int ps_tem_plan(const PsTemDesc* desc, const PsTemTensors* params, int32_t has_valid, PsEncPath* out) {
   PS_REQUIRE(desc && out, "plan: null argument");
-  PsTemDesc D = *desc;
-  if (D.C > 0) D.training = 0;                  // an eval call (ps_tem_score); C == 0: ps_tem_forward / ps_tem_backward
-  Ws w;
-  TRY(make_ws(D, w));
-  // enc_plan tests pointers against null and adds offsets to the workspace base, nothing more: stand-ins that are never read
+  const TemCall t(desc, TEM_DESCRIBED, nullptr);
+  TRY(t.rc);
+  const PsTemDesc& D = t.D;
+  // enc_call tests pointers against null and adds offsets to the workspace base, nothing more: stand-ins that are never read
   static float stand_in[4];
   PsTemTensors all;
   memset(&all, 0, sizeof(all));
@@ -310,7 +309,7 @@ extern "C" int ps_tem_plan(const PsTemDesc* desc, const PsTemTensors* params, in
     const float** slot = reinterpret_cast<const float**>(&all);
     for (size_t k = 0; k < sizeof(all) / sizeof(float*); ++k) slot[k] = stand_in;
   }
-  const EncPlan pl = enc_plan(D, params ? *params : all, stand_in, w, rows_list_ok(D), has_valid ? stand_in : nullptr);
+  const EncPlan pl = enc_call(t.base(params ? *params : all, stand_in), nullptr, has_valid ? stand_in : nullptr, t.listed).plan;
   memset(out, 0, sizeof(*out));
   const bool enc = D.model == PS_MODEL_TEM && D.n_layers > 0;
   out->n_layers = enc ? D.n_layers : 0;
@@ -328,13 +327,12 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
                              ps_stream_t stream, EncBwdOut& out) {
   PS_REQUIRE(desc && params && batch && ws && grads, "backward: null argument");
   enc_taken_clear(1, 0);                          // (QEM / AEM / ZAM: no encoder layers; enc_layers_backward fills it otherwise)
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
+  const TemCall t(desc, TEM_TRAIN, stream);
+  TRY(t.rc);
+  const PsTemDesc& D = t.D; const Ws& w = t.w; hipStream_t st = t.st;
   const PsTemTensors& P = *params;
   const PsTemTensors& G = *grads;
+  const EncCall c = t.enc(P, ws, batch->u_item_idxs, st);
   const bool tem = D.model == PS_MODEL_TEM;
   const int B = D.B, d = D.d, S = w.S, NL = tem ? D.n_layers : 0;
   const float* hist = D.sep_prod_emb ? P.hist_product_emb : P.product_emb;
@@ -347,7 +345,7 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
 
   // 1. loss + score backward: d enc, table-row scatter-adds
   ScoreArgs s;
-  fill_score(D, P, *batch, ws, w, s);
+  fill_score(c, *batch, s);
   s.scale = loss_scale; s.scale_dev = loss_scale_dev; s.denc = ws + w.denc;
   s.g_product_emb = G.product_emb; s.g_word_emb = G.word_emb; s.g_product_bias = G.product_bias;
   s.g_word_bias = G.word_bias;
@@ -365,13 +363,13 @@ static int tem_backward_impl(const PsTemDesc* desc, const PsTemTensors* params, 
   int lddqe = d;
   if (tem) {
     EncBwdIn in;
-    in.fold = &fold; in.score_on_side = score_deferred ? &s : nullptr; in.rows_listed = rows_list_ok(D);
+    in.fold = &fold; in.score_on_side = score_deferred ? &s : nullptr;
     in.caller_flushes_tail = true;     // out.wg3_last and out.score_words_last: this function's last launches
-    TRY(enc_layers_backward(D, P, G, batch->u_item_idxs, nullptr, ws, w, st, in, out));
+    TRY(enc_layers_backward(c, G, in, out));
     dqe = ws + w.dx;      // row 0 of each sequence is the query embedding
     lddqe = S * d;
   } else if (ps_model_attn(D.model)) {
-    TRY(ae_backward(D, P, G, batch->u_item_idxs, ws, w, st));
+    TRY(ae_backward(c, G));
     dqe = ws + w.ae_dqe;
   }
 
@@ -464,45 +462,29 @@ extern "C" int ps_graph_replay_enabled(void) { return ps_graphs_enabled() ? 1 : 
 // where ps_tem_forward_step staged the call's index tensors (for an eager ps_tem_backward after a replayed forward)
 extern "C" int ps_tem_staged_batch(const PsTemDesc* desc, float* workspace, PsTemBatch* out) {
   PS_REQUIRE(desc && workspace && out, "staged_batch: null argument");
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  *out = staged_batch(stage_layout(D, workspace, w));
+  const TemCall t(desc, TEM_TRAIN, nullptr);
+  TRY(t.rc);
+  *out = staged_batch(stage_layout(t.D, workspace, t.w));
   return PS_OK;
 }
 
 // forward of one training step with the caller-varying inputs routed through the staging prologue, so that the launch
 // sequence can be captured once per shape and replayed.  sampler_prob/alias non-null: negatives are drawn in the
 // prologue (batch->neg_* ignored), else batch->neg_* are staged like the other index tensors.
-static int forward_body(const PsTemDesc& D, const PsTemTensors& P, const StageArgs& sa, const PsTemBatch& Bs, float* ws,
-                        const Ws& w, float* loss3, float* loss_acc, hipStream_t st) {
-  TRY(launch_stage(sa, st));
-  TRY(encode_forward(D, P, Bs, ws, w, st));
-  ScoreArgs s;
-  fill_score(D, P, Bs, ws, w, s);
-  s.loss3 = loss3; s.loss_acc = loss_acc;
-  TRY(launch_score_fwd(s, st));
-  TRY(launch_loss(s, st));
-  return PS_OK;
-}
-
 extern "C" int ps_tem_forward_step(const PsTemDesc* desc, const PsTemTensors* params, const PsTemBatch* batch,
                                    const float* sampler_prob, const int32_t* sampler_alias, float* workspace,
                                    float* loss3, float* loss_acc, ps_stream_t stream) {
   PS_REQUIRE(desc && params && batch && workspace && loss3, "forward_step: null argument");
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
+  const TemCall t(desc, TEM_TRAIN, stream);
+  TRY(t.rc);
+  const PsTemDesc& D = t.D;
   const bool sampled = sampler_prob && sampler_alias;
   const bool hist = D.model == PS_MODEL_TEM || ps_model_attn(D.model);
   PS_REQUIRE(batch->query_word_idxs && batch->target_prod_idxs && (!hist || batch->u_item_idxs) &&
              (D.W == 0 || batch->pos_iword_idxs), "forward_step: null batch tensors");
   PS_REQUIRE(sampled || (batch->neg_item_idxs && (D.W == 0 || batch->neg_word_idxs)), "forward_step: no negatives");
   PS_REQUIRE(params->word_bias && (!D.bias_product || params->product_bias), "forward_step: null bias tensors");
-  const StageLayout L = stage_layout(D, workspace, w);
+  const StageLayout L = stage_layout(D, workspace, t.w);
   const PsTemBatch Bs = staged_batch(L);
   StageArgs sa;
   memset(&sa, 0, sizeof(sa));
@@ -517,7 +499,6 @@ extern "C" int ps_tem_forward_step(const PsTemDesc* desc, const PsTemTensors* pa
     sa.k0 = (uint32_t)(D.seed & 0xffffffffu); sa.k1 = (uint32_t)(D.seed >> 32);
   }
   ps_step_ptr_slot() = L.step_word;               // every DropSpec built below reads the step from the workspace
-  int rc = PS_OK;
   PsGraphEntry* e = nullptr;
   if (ps_graphs_enabled()) {
     PsTemDesc Dk = D;
@@ -529,34 +510,18 @@ extern "C" int ps_tem_forward_step(const PsTemDesc* desc, const PsTemTensors* pa
     for (int k = 0; k < 6; ++k) { const int has = sa.src[k] != nullptr; key = ps_fnv(key, &has, sizeof(has)); }
     e = ps_graph_lookup(key);
   }
+  ScoreArgs s;                                    // a replay's loss-kernel arguments
   if (e && e->state == 2) {
-    ScoreArgs s;
-    fill_score(D, *params, Bs, workspace, w, s);
+    fill_score(t.base(*params, workspace), Bs, s);
     s.loss3 = loss3; s.loss_acc = loss_acc; s.loss_nblk = score_fwd_blocks(s);
-    void* p0[1] = {(void*)&sa};
-    void* p1[1] = {(void*)&s};
-    rc = ps_graph_patch(e, 0, p0) || ps_graph_patch(e, 1, p1) || ps_graph_launch(e, st);
-    if (rc) ps_set_error("forward_step: graph replay failed");
-  } else {
-    hipStream_t cap = (e && e->state == 1) ? ps_graph_begin() : nullptr;
-    if (cap) {
-      rc = forward_body(D, *params, sa, Bs, workspace, w, loss3, loss_acc, cap);
-      const void* patch[2] = {stage_kernel_handle(), loss_kernel_handle()};
-      if (ps_graph_end(cap, e, patch, 2) == PS_OK && rc == PS_OK) rc = ps_graph_launch(e, st);
-      else { e->state = -1; rc = forward_body(D, *params, sa, Bs, workspace, w, loss3, loss_acc, st); }
-    } else {
-      if (e && e->state == 0) e->state = 1;
-      rc = forward_body(D, *params, sa, Bs, workspace, w, loss3, loss_acc, st);
-    }
   }
+  const PsGraphPatch patch[2] = {{stage_kernel_handle(), &sa}, {loss_kernel_handle(), &s}};
+  // (never folded, captured or not: may_fold = false)
+  const int rc = ps_graph_step(e, t.st, "forward_step", patch, 2, [&](hipStream_t on) {
+    return tem_forward(t.enc(*params, workspace, Bs.u_item_idxs, on), Bs, nullptr, loss3, loss_acc, false, &sa);
+  });
   ps_step_ptr_slot() = nullptr;
   return rc;
-}
-
-static int backward_body(const PsTemDesc& D, const PsTemTensors& P, const PsTemBatch& Bs, float* ws, const PsTemTensors& G,
-                         float loss_scale, float* zero_ptr, int64_t zero_floats, hipStream_t st) {
-  if (zero_ptr && zero_floats > 0) PS_CHECK_HIP(hipMemsetAsync(zero_ptr, 0, sizeof(float) * (size_t)zero_floats, st));
-  return ps_tem_backward(&D, &P, &Bs, ws, &G, loss_scale, nullptr, st);
 }
 
 // backward of the step ps_tem_forward_step ran last on this workspace (its staged indices and step word are reused);
@@ -565,18 +530,14 @@ extern "C" int ps_tem_backward_step(const PsTemDesc* desc, const PsTemTensors* p
                                     const PsTemTensors* grads, float loss_scale, float* zero_ptr, int64_t zero_floats,
                                     ps_stream_t stream) {
   PS_REQUIRE(desc && params && ws && grads, "backward_step: null argument");
-  PsTemDesc D = *desc;
-  D.C = 0;
-  Ws w;
-  TRY(make_ws(D, w));
-  hipStream_t st = (hipStream_t)stream;
-  const StageLayout L = stage_layout(D, ws, w);
+  const TemCall t(desc, TEM_TRAIN, stream);
+  TRY(t.rc);
+  const StageLayout L = stage_layout(t.D, ws, t.w);
   const PsTemBatch Bs = staged_batch(L);
   ps_step_ptr_slot() = L.step_word;
-  int rc = PS_OK;
   PsGraphEntry* e = nullptr;
   if (ps_graphs_enabled()) {
-    PsTemDesc Dk = D;
+    PsTemDesc Dk = t.D;
     Dk.step = 0;
     uint64_t key = ps_fnv(PS_FNV0, "bwd", 3);
     key = ps_fnv(key, &Dk, sizeof(Dk)); key = ps_fnv(key, params, sizeof(*params)); key = ps_fnv(key, grads, sizeof(*grads));
@@ -584,20 +545,10 @@ extern "C" int ps_tem_backward_step(const PsTemDesc* desc, const PsTemTensors* p
     key = ps_fnv(key, &zero_ptr, sizeof(zero_ptr)); key = ps_fnv(key, &zero_floats, sizeof(zero_floats));
     e = ps_graph_lookup(key);
   }
-  if (e && e->state == 2) {
-    rc = ps_graph_launch(e, st);
-    if (rc) ps_set_error("backward_step: graph replay failed");
-  } else {
-    hipStream_t cap = (e && e->state == 1) ? ps_graph_begin() : nullptr;
-    if (cap) {
-      rc = backward_body(D, *params, Bs, ws, *grads, loss_scale, zero_ptr, zero_floats, cap);
-      if (ps_graph_end(cap, e, nullptr, 0) == PS_OK && rc == PS_OK) rc = ps_graph_launch(e, st);
-      else { e->state = -1; rc = backward_body(D, *params, Bs, ws, *grads, loss_scale, zero_ptr, zero_floats, st); }
-    } else {
-      if (e && e->state == 0) e->state = 1;
-      rc = backward_body(D, *params, Bs, ws, *grads, loss_scale, zero_ptr, zero_floats, st);
-    }
-  }
+  const int rc = ps_graph_step(e, t.st, "backward_step", nullptr, 0, [&](hipStream_t on) -> int {
+    if (zero_ptr && zero_floats > 0) PS_CHECK_HIP(hipMemsetAsync(zero_ptr, 0, sizeof(float) * (size_t)zero_floats, on));
+    return ps_tem_backward(&t.D, params, &Bs, ws, grads, loss_scale, nullptr, on);
+  });
   ps_step_ptr_slot() = nullptr;
   if (rc != PS_OK) side_abort();
   return rc;

@@ -129,6 +129,23 @@ def test_deterministic_mode_drops_the_two_unordered_forms(lib):
     assert ep.diff(det, base) == {'item_scatter': (0, 1), 'dx_fused': (0, 1)}
 
 
+def test_a_setter_between_two_calls_changes_the_next_plan(lib):
+    """The call context is built per entry call and latches no setter: ps_set_item_scatter_fused(0) changes the very next plan,
+    by that cell alone, and restoring it restores the plan in the same process."""
+    if not ep.default_switches():
+        pytest.skip("default switches only")
+    r = next(r for r in ep.ALL_ROWS if r['name'] == 'e_50_20_9')
+    base = ep.plan_of(lib, _lib, ep.desc_of(r, _lib))
+    old = lib.ps_set_item_scatter_fused(0)
+    try:
+        off = ep.plan_of(lib, _lib, ep.desc_of(r, _lib))
+    finally:
+        lib.ps_set_item_scatter_fused(old)
+    assert old == 1 and base['item_scatter'] == 1
+    assert ep.diff(off, base) == {'item_scatter': (0, 1)}
+    assert ep.plan_of(lib, _lib, ep.desc_of(r, _lib)) == base
+
+
 # ---- the supported switches: each child calls ps_tem_plan on these four rows and nothing else
 PROBES = ('e_50_20_9', 'mf1008', 'w_d256', 'e_6_4_40_nodrop')
 # switch -> {probe: (layer-0 form, flags)}; a probe not named keeps its table row
